@@ -14,6 +14,11 @@ Launch:  python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1 and no W
                                                                   own N ranks, one per GPU, before anything touches a GPU)
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and no more: set up, W warm-up steps, K timed steps, the line (value, ms_per_step, the
+stage times of the timed steps and the roofline arithmetic on them).  --full adds everything that takes runs of its own: the
+assignment / relaxed / filter extras, the shader clock probe, the counter traffic and shell maxima of the roofline record, the
+CPU baselines.  --dump-outputs DIR writes what the last timed step computed (rank 0's share) as DIR/<name>.npy, see dump_outputs.
 """
 import argparse
 import json
@@ -321,6 +326,53 @@ def dry_run(args):
                           "spawned": os.environ.get("PM_BENCH_SPAWNED") == "1", "local_rank": int(os.environ.get("LOCAL_RANK", "0"))}), flush=True)
 
 
+DUMP_SEED = 20240607           # of the fixed sample --dump-outputs takes of the outputs that are too large to write whole
+DUMP_COST_ENTRIES = 1 << 18    # entries per cost matrix (8 x 2 MiB of float64)
+DUMP_DESCRIPTOR_ROWS = 1024    # descriptor rows per cloud ((2 + 4) x 1024 x 360 float64 = 17.7 MB)
+
+
+def dump_outputs(path, U, sc_m, sc_f, stats, A, res):
+    """--dump-outputs: what the last timed step handed to its caller, as <path>/<name>.npy in float64 (35 MB at 50k):
+      icp_affine [4, 4], icp_residuals [iterations]            whole
+      centroid_* [3], mean_distance_* [1], pca_axis_* [3]      whole (moving, fixed)
+      descriptors_moving [2, r, 360], descriptors_fixed [f, r, 360]   a seeded sample of r rows (all of them when the cloud is smaller);
+                                                                      f = 4, or 1 where a sharded step gathered frame 1 alone
+      cost_sample [8, k]                                       the same k seeded (row, column) entries of each of the eight matrices
+    The sample depends on DUMP_SEED and the shapes alone, so two builds run with the same arguments write the same entries.  A
+    sharded run writes rank 0's row block."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def host(x):
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        return np.ascontiguousarray(x, dtype=np.float64).reshape(x.shape if x.ndim else (1,))
+
+    def save(name, x):
+        np.save(os.path.join(path, name + ".npy"), host(x))
+
+    def some_rows(t):
+        rows = t.shape[1]
+        if rows <= DUMP_DESCRIPTOR_ROWS:
+            return t
+        pick = np.sort(rng.choice(rows, size=DUMP_DESCRIPTOR_ROWS, replace=False))
+        return t[:, torch.as_tensor(pick, device=t.device)]
+
+    save("icp_affine", A.reshape(4, 4))
+    save("icp_residuals", res)
+    for cloud, (c, md, x0) in zip(("moving", "fixed"), stats):
+        save("centroid_" + cloud, c)
+        save("mean_distance_" + cloud, md)
+        save("pca_axis_" + cloud, x0)
+    save("descriptors_moving", some_rows(sc_m))
+    save("descriptors_fixed", some_rows(sc_f))
+    _, rows, cols = U.shape
+    k = min(DUMP_COST_ENTRIES, rows * cols)
+    flat = np.sort(rng.choice(rows * cols, size=k, replace=False)) if k < rows * cols else np.arange(k)
+    r_idx, c_idx = (torch.as_tensor(x, device=U.device) for x in (flat // cols, flat % cols))
+    save("cost_sample", U[:, r_idx, c_idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -332,9 +384,17 @@ def main():
     ap.add_argument("--no-cpu-config2", action="store_true", help="skip the fully timed host run of BASELINE config 2 (5 000 nuclei, ~1 min of CPU)")
     ap.add_argument("--no-assignment", action="store_true", help="skip the untimed extra leg (eight assignments of the same build)")
     ap.add_argument("--dry-run", action="store_true", help="launcher + rendezvous only (gloo, no GPU): what the CPU test-suite runs")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline: assignment, relaxed and filter extras, shader clock, "
+                                                        "counter traffic, shell maxima, CPU baselines (the --no-* switches take legs out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float64; large outputs as a "
+                                                          "fixed seeded sample, 35 MB in all at 50k; rank 0's share of a sharded run)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                            # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_cpu_config2 = args.no_assignment = True
 
     # One process asked for several GPUs (the driver's `python bench.py --gpus N`): start the N ranks as fresh children
     # BEFORE torch is imported or a GPU is touched, relay rank 0's line, return the worst child's exit code.
@@ -414,6 +474,7 @@ def main():
             symmetric[0] = sc_f.shape[0] == 1
         if marks: marks[2].record()
         sc_m_last[0], sc_f_last[0] = sc_m, sc_f
+        stats_last[0] = ((cm, mdm, x0m), (cf, mdf, x0f))
         if symmetric[0]:
             K.chi2_cost8_frame1(sc_m[0], sc_f[0], out=U, info=table_info if marks is None else None)   # (report read back in warm-up only)
         else:
@@ -431,7 +492,7 @@ def main():
 
     symmetric = [False]                          # which chi-square kernel the last step's descriptors selected
     table_info = {}                              # which shells the half-cost kernel took from its term table
-    sc_m_last, sc_f_last = [None], [None]
+    sc_m_last, sc_f_last, stats_last = [None], [None], [None]
 
     def fence():
         torch.cuda.synchronize()
@@ -452,6 +513,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
         elapsed = float(t.item())
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:          # before any extra launch writes into U again
+        dump_outputs(args.dump_outputs, U, sc_m_last[0], sc_f_last[0], stats_last[0], A, res)
 
     stage = np.array([[ev[k][i].elapsed_time(ev[k][i + 1]) for i in range(4)] for k in range(args.steps)]).mean(0)  # ms
     chi2_ms = float(stage[2])
@@ -462,7 +525,7 @@ def main():
     # running-sum adds = 48 instructions, 68 flop (fma = 2); general kernel: 8 terms x 11 instructions, 128 flop.
     # Issue model (measured, tools/microbench/fp64_issue.hip + SQ counters): 4 cycles per instruction, 16 for v_rcp_f64.
     sym = bool(symmetric[0])
-    if sym and not table_info:                   # no warm-up step ran: one untimed launch for the report
+    if sym and not table_info and args.full:     # no warm-up step ran: one untimed launch for the report
         K.chi2_cost8_frame1(sc_m_last[0][0], sc_f_last[0][0], out=U, info=table_info)
     tabled = sum(table_info.get("tabled_shells", [])) if sym else 0
     ft = tabled / 30.0                           # fraction of the (pair, bin) terms served from the table
@@ -477,16 +540,18 @@ def main():
 
     add_floor_s = 8.0 * 360.0 * rows * m / 64.0 / 1024.0 * 4.0 / 2.4e9      # the running-sum adds alone (183 ms at 50k)
     # HBM traffic of that launch: from the committed rocprofv3 PMC passes of this configuration (1 GPU, this N), else null
-    traffic, traffic_src = pmc_traffic("chi2_sym_kernel" if sym else "chi2_kernel<", n) if world == 1 else (None, None)
+    traffic, traffic_src = pmc_traffic("chi2_sym_kernel" if sym else "chi2_kernel<", n) if world == 1 and args.full else (None, None)
     traffic_why = None
-    if traffic is None:
+    if not args.full:
+        traffic_why = "the committed PMC passes are looked up with --full only"
+    elif traffic is None:
         traffic_why = ("no PMC pass of this configuration is committed: profiles/pmc_traffic.json holds the 1-GPU N = M = 50 000 launch"
                        + ("; a rank's row block reads the same descriptors and writes rows/%d of the matrices (the launch is linear in "
                           "its rows, profiles/r04_chi2_blocks.txt)" % world if world > 1 else ""))
 
     # per-shell maxima of the integer counts behind the descriptors (what decides which shells the 94 x 94 term table can serve)
     shell_max = None
-    if sym:
+    if sym and args.full:
         def shell_maxima(sc1):
             pos = sc1[sc1 > 0]
             tot = float(torch.round(1.0 / pos.min())) if pos.numel() else 1.0
@@ -681,7 +746,7 @@ def main():
             "metric": "point-pairs/s (shape-context + chi2 cost + ICP)",
             "value": n * m / (ms_per_step * 1e-3),
             "unit": "point-pairs/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "full": bool(args.full),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": "BASELINE configs[2]+north_star 50k build: N=M=%d synthetic clouds, descriptors (2+4 frames), "
                                    "8 chi2 cost matrices to HBM, %d-iteration affine ICP" % (n, args.icp_iters),

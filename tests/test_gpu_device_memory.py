@@ -31,6 +31,15 @@ def _driver_free():
     return torch.cuda.mem_get_info()[0]
 
 
+def _driver_drop(nbytes):
+    """The least the driver's free figure must fall by when it hands out a block of nbytes.  The figure is not exact to the byte:
+    on an otherwise idle MI355X a fresh 5 GiB block moves it by 5 GiB - 10 MiB and a 6 GiB block by 6 GiB - 12 MiB, that is by
+    1/512 less than the block (the size of a block's page-table entries, 8 bytes per 4 KiB page, which the driver's figure
+    appears to have set aside beforehand).  Twice that share is allowed for; a block served from a cache moves the figure by
+    nothing at all, which is what the assertion is there to tell apart."""
+    return nbytes - nbytes // 256
+
+
 def test_small_requests_stay_with_torch_and_big_ones_are_raw_blocks(dm):
     import torch
     before = dm.stats()
@@ -39,7 +48,7 @@ def test_small_requests_stay_with_torch_and_big_ones_are_raw_blocks(dm):
     free0 = _driver_free()
     big = dm.big_empty((5, 1 << 27), torch.float64, "cuda")                      # 5 GiB
     assert dm.stats()["raw_allocations"] == before.get("raw_allocations", 0) + 1
-    assert free0 - _driver_free() >= 5 << 30                                     # the driver handed it out now, not torch's cache
+    assert free0 - _driver_free() >= _driver_drop(5 << 30)                       # the driver handed it out now, not torch's cache
     assert big.shape == (5, 1 << 27) and big.dtype == torch.float64 and big.is_contiguous() and big.data_ptr() % 256 == 0
     big.fill_(1.5)
     assert float(big[4, -1]) == 1.5 and float(big.sum()) == 1.5 * 5 * (1 << 27)
@@ -77,7 +86,7 @@ def test_idle_blocks_are_bounded_and_unkept_blocks_go_back_at_once(dm, monkeypat
     dm.trim()
     free0 = _driver_free()
     t = dm.big_empty((6 << 30,), torch.uint8, "cuda", keep=False)
-    assert free0 - _driver_free() >= 6 << 30
+    assert free0 - _driver_free() >= _driver_drop(6 << 30)
     del t
     gc.collect()
     assert dm.idle_bytes() == 0 and _driver_free() >= free0 - (64 << 20)

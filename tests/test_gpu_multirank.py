@@ -94,7 +94,7 @@ def test_bench_step_on_two_ranks_sharing_the_gpu():
     """`python bench.py --gpus 2` through its own launcher, the ranks put on cuda:0 and gloo in RCCL's place (rehearsal
     switches of bench.py): the sharded step end to end, one JSON line from rank 0."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--points", "6000",
-                        "--icp-iters", "5", "--no-cpu-baseline"], env=_env(PM_BENCH_ONE_DEVICE="1", PM_BENCH_BACKEND="gloo"),
+                        "--icp-iters", "5", "--full", "--no-cpu-baseline"], env=_env(PM_BENCH_ONE_DEVICE="1", PM_BENCH_BACKEND="gloo"),
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -121,7 +121,7 @@ def test_bench_line_survives_a_sharded_extra_that_does_not_return():
     must still print its one JSON line (the extra reported as timed out, no CPU baseline touching the device afterwards) and every
     rank must leave with exit code 0 without the closing barrier."""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--points", "6000",
-                        "--icp-iters", "3"], env=_env(PM_BENCH_ONE_DEVICE="1", PM_BENCH_BACKEND="gloo", PM_BENCH_EXTRA_TIMEOUT_S="0.001"),
+                        "--icp-iters", "3", "--full"], env=_env(PM_BENCH_ONE_DEVICE="1", PM_BENCH_BACKEND="gloo", PM_BENCH_EXTRA_TIMEOUT_S="0.001"),
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-2500:])
     line = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -18,7 +18,7 @@ for JOB in "$@"; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 ;;
     bench)      # the headline line (N = M = 50 000) with the CPU baseline and both extras
-      timeout -k 10 600 python bench.py --steps ${STEPS:-20} --warmup 2 > $O/${TAG}_bench50k.json 2> $O/${TAG}_bench50k.err; tail -c 400 $O/${TAG}_bench50k.json ;;
+      timeout -k 10 600 python bench.py --full --steps ${STEPS:-20} --warmup 2 > $O/${TAG}_bench50k.json 2> $O/${TAG}_bench50k.err; tail -c 400 $O/${TAG}_bench50k.json ;;
     profile)    # rocprofv3 kernel trace of the bench command + the two PMC passes (separate runs, kernel-trace only beside --pmc)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o bench -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-assignment > $O/${TAG}_prof.log 2>&1
       timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${TAG}_pmc_FETCH -- python3 tools/profile_build.py > $O/${TAG}_pmc_fetch.log 2>&1
