@@ -265,6 +265,27 @@ int pm_lsap_certificate_f32(const float *U, int nr, int nc, size_t ld, const dou
                             double delta, double eps, int32_t *summary4, double *stats2, int32_t *tight, double *tight_red, int cap,
                             double *row_slack, double *row_neg, void *stream);
 
+/* Per-row CANDIDATES from the Hellinger lower bound of the cost, on the matrix cores (csrc/pm_hellinger.hip): for a, b >= 0,
+ * (a-b)^2/(a+b) >= (sqrt a - sqrt b)^2, so C(i,j) >= L(i,j) = 0.5 (sum a_i + sum b_j) - sum_k sqrt(a_ik) sqrt(b_jk) — a float32 GEMM
+ * of the sqrt-descriptors (v_mfma_f32_32x32x2f32), fused with a per-row top-k: no N x M matrix is written.
+ *   scA    [nA][360], one moving frame (or one rank's row block of it);  scB + f * frame_stride: fixed frame f, [nB][360] each;
+ *   n_frames 1..4, k 1..64;  split: workgroups the fixed rows are divided over per block of 64 moving rows, 0 = automatic
+ *   (the result does not depend on it, bit for bit);
+ *   out_col, out_bound  [n_frames][nA][k], ascending by (bound, column); where fewer than k columns can be listed (nB < k,
+ *   non-finite fixed rows) the tail holds column -1 and bound +inf; a non-finite moving row gets -1 and NaN throughout.  A row
+ *   is non-finite if it holds a NaN, an infinity or a negative value; such fixed rows are never listed.  nonfinite1[0] = 1 if
+ *   any descriptor row of either side was non-finite, else 0.
+ * CONTRACT, for descriptor rows with sum <= 1 and delta = pm_hellinger_delta: every listed entry has C(i, col) >= bound - delta,
+ * and every column j that is NOT listed and whose fixed row is finite has C(i, j) >= bound[k-1] - delta.
+ * The frames are given explicitly (with the fixed cloud's four frames: the bounds of U11, U12, U13, U14), so the symmetry
+ * precondition of the *_sym builds does not apply.  ws: pm_hellinger_topk_workspace bytes, 16-byte aligned device memory.
+ * pm_hellinger_delta is a HOST function: it writes the constant to host memory. */
+size_t pm_hellinger_topk_workspace(int nA, int nB, int n_frames, int k);
+int pm_hellinger_topk(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames, int k,
+                      int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1, void *ws, size_t ws_bytes,
+                      void *stream);
+int pm_hellinger_delta(double *delta1_host);
+
 /* Listed entries of one pairing's two EXACT matrices (the bits of pm_chi2_cost_pair_sym's): out_natural[e], out_rolled[e] =
  * entry (rows[e], cols[e]) of the natural-order matrix (U11, U12, U13, U14 for pairing 0..3) and of its rolled-order twin (U22,
  * U21, U24, U23).  rows / cols / outputs: device, n_entries each; an index out of range yields NaN in both outputs.  What turns

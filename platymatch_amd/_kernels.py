@@ -390,6 +390,47 @@ def chi2_filter_delta():
     return float(nat.load().pm_chi2_filter_delta())
 
 
+def hellinger_topk(sc_a, sc_b, k=16, split=0, info=None):
+    """Per row of sc_a [N, 360] the k columns of each fixed frame sc_b [F, M, 360] (or [M, 360]: F = 1) with the smallest
+    Hellinger lower bound of the chi-square cost, on the matrix cores (pm_hellinger_topk; csrc/pm_hellinger.hip) ->
+    (cols int32 [F, N, k], bound float64 [F, N, k]), ascending by (bound, column); -1 / +inf where fewer than k columns can be
+    listed, -1 / NaN for a non-finite row of sc_a.  Exact cost >= bound - hellinger_delta() for listed entries, >= bound[..., -1] -
+    hellinger_delta() for every other column.  split: workgroups per block of 64 rows (0 = automatic; same bits for any value).
+    info (dict): receives 'nonfinite' (synchronises)."""
+    torch = _t()
+    a = _desc(sc_a, "sc_a")
+    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
+            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
+        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
+    _here(sc_b, "sc_b")
+    k, split = int(k), int(split)
+    if not 1 <= k <= 64:
+        raise ValueError("k must be 1..64")
+    if split < 0:
+        raise ValueError("split must be >= 0 (0 = automatic)")
+    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
+    N, M = a.shape[0], sc_b.shape[-2]
+    lib = nat.load()
+    cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
+    bound = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
+    flag = torch.empty(1, dtype=torch.int32, device=a.device)
+    ws = nat.workspace(lib.pm_hellinger_topk_workspace(N, M, F, k), a.device)
+    check(lib.pm_hellinger_topk(ptr(a), N, ptr(sc_b), M, M * NBINS, F, k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws), ws.numel(),
+                                nat.stream_ptr()))
+    if info is not None:
+        info["nonfinite"] = int(flag.item())
+    return cols, bound
+
+
+def hellinger_delta():
+    """Absolute error bound of hellinger_topk's bounds against the float64 Hellinger bound, for descriptor rows that sum to at
+    most 1 (csrc/pm_hellinger.hip: PM_HELLINGER_DELTA)."""
+    import ctypes
+    d = ctypes.c_double(0.0)
+    check(nat.load().pm_hellinger_delta(ctypes.addressof(d)))
+    return float(d.value)
+
+
 def chi2_entries(sc_m1, sc_f1, pairing, rows, cols, trusted=False):
     """Listed entries (rows[e], cols[e]) of pairing t's two EXACT matrices -> (natural-order values, rolled-order values), float64
     GPU tensors [len(rows)] carrying the bits of chi2_cost_pair's matrices (pm_chi2_entries_sym).  rows / cols: integer arrays

@@ -16,12 +16,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libplatymatch_hip.so")
-SOURCES = ["pm_api.hip", "pm_stats.hip", "pm_shape_context.hip", "pm_chi2.hip", "pm_transform.hip",
+SOURCES = ["pm_api.hip", "pm_stats.hip", "pm_shape_context.hip", "pm_chi2.hip", "pm_hellinger.hip", "pm_transform.hip",
            "pm_icp.hip", "pm_icp_grid.hip", "pm_similar.hip", "pm_ransac.hip", "pm_eval.hip", "pm_lsap_dev.hip", "pm_lsap_resident.hip", "pm_lsap.cpp", "pm_lsap_core.cpp",
            "pm_host_rng.cpp"]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-ffp-contract=off", "-fno-fast-math",
          "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
+# per-file additions.  pm_hellinger.hip: its float32 work belongs to the matrix cores; the few scalar float32 operations around
+# them are not to be fused into packed ones (the filter build's packed arithmetic is written by hand where it is wanted).
+EXTRA_FLAGS = {"pm_hellinger.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc():
@@ -99,7 +102,7 @@ def build_native(force=False, verbose=False):
                 jobs.append([shutil.which("g++") or "g++", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
                              "-Wall", "-c", s, "-o", o])
             else:
-                jobs.append([hipcc] + FLAGS + ["-c", s, "-o", o])
+                jobs.append([hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + ["-c", s, "-o", o])
 
     def run(cmd):
         if verbose:

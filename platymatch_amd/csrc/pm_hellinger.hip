@@ -1,0 +1,443 @@
+// pm_hellinger.hip — the Hellinger lower bound of the chi-square cost on the matrix cores, fused with a per-row top-K.
+//
+// For a, b >= 0:  (a-b)^2/(a+b) = (sqrt a - sqrt b)^2 (sqrt a + sqrt b)^2/(a+b) >= (sqrt a - sqrt b)^2,  hence
+//     C(i,j) = 0.5 sum_k (a_k-b_k)^2/(a_k+b_k)  >=  L(i,j) = 0.5 (sum a + sum b) - sum_k sqrt(a_k) sqrt(b_k).
+// The last sum is a GEMM of the sqrt-descriptors, N x 360 by 360 x M per fixed frame: 2*360 flop per pair where the filter
+// build (pm_chi2.hip: filter4_kernel) issues ~5.5 slots per TERM, half of them v_rcp_f32.  Nothing of the N x M product is
+// stored: each row keeps its k smallest bounds (k <= 64) and the columns they belong to.
+//
+// Layout.  hl_prep_kernel writes float32 sqrt-descriptors (sqrt taken in float64, rounded once to float32) in BLOCKS of 64
+// rows, bin-major inside a block: element (row r, bin q) of a block sits at  q*64 + ((r + 32 (q & 1)) & 63).  A block is
+// 92 160 contiguous bytes, and a 40-bin chunk of it 10 240, so global -> LDS is a straight 16-byte copy (no transposition,
+// no LDS write conflicts).  v_mfma_f32_32x32x2f32 wants, from lane l, operand element (row l % 32, bin 2 m + l / 32): with
+// the rotation by 32 on odd bins the 64 lanes of one ds_read_b32 touch 64 distinct banks (and each half-wave 32 distinct
+// ones), without a padding column.  Rows past the end of a cloud and non-finite rows (a NaN, an infinity, a negative value,
+// or a sum that overflows) are zero rows, so the GEMM stays finite; their half row sum h = 0.5 sum is replaced by NaN
+// (moving side) or +inf (fixed side) — that value IS the row's flag: a NaN bound never passes a comparison, a +inf bound is
+// never listed, and the epilogue needs no masks for ragged edges.
+//
+// Main kernel (hl_topk_kernel), one 256-thread workgroup per (block of 64 moving rows, column split s, fixed frame):
+//   - the block's 64 x 360 sqrt-rows stay in LDS (92 KB) for the whole sweep;
+//   - tiles of 64 fixed rows stream through two LDS stages of 40 bins (2 x 10 KB), the next stage travelling through
+//     registers while the current one is multiplied: one barrier per stage of 20 MFMAs per wave;
+//   - wave w owns the 32 x 32 quadrant (rows 32 (w & 1), columns 32 (w >> 1)): 180 chained v_mfma_f32_32x32x2f32 per tile
+//     into 16 accumulation registers, always bins 0..359 in order — an entry's bits do not depend on the launch geometry;
+//   - epilogue in registers: L~ = (hA_i + hB_j) - (double)dot against tau_i (LDS), the row's current k-th smallest bound;
+//     an entry with L~ <= tau_i (ties kept: the order is by (bound, column)) is appended — (dot, column), 8 bytes — to the
+//     row's buffer of HL_CAP = 80 slots.  A full buffer is cut back to its k smallest by (bound, column) by one wave (ranks
+//     by counting, 80 x 80 comparisons) and tau_i lowered; lanes whose append found no slot retry after the cut.  After the
+//     first tiles appends are rare (~ k ln(M / k) per row), so the sweep runs at the speed of its MFMAs.
+//   LDS: 92 160 + 20 480 + 40 960 (buffers) + 2 560 (ranking scratch) + 1 300 = 157 460 B: ONE workgroup per CU, one wave
+//   per SIMD — the occupancy this kernel is built for (its 136 registers are not the limit; nothing spills).
+//   Measured (profiles/hellinger_*): 22.2 ms for 20 000 x 20 000 x 4 frames, k = 16 — a third of the float32 matrix peak.
+// Few row blocks: the fixed rows' tiles are split over S workgroups per (block, frame), each writes its sorted k-list to the
+// workspace, hl_merge_kernel merges the S lists of a row by (bound, column) (one wave per row, a k-round tournament over
+// the list heads).  Column sets are disjoint and every list is an exact top-k of its set, so the result is the same for any S.
+//
+// Error bound.  PM_HELLINGER_DELTA bounds |L~ - L| for descriptor rows with sum a, sum b <= 1, with no assumption about the
+// MFMA's internal rounding or summation order: u = 2^-24; each input sqrt is rounded once to float32 (after a correctly
+// rounded float64 sqrt: (1 + 2^-53) u), so |ra rb - sqrt a sqrt b| <= (2u + u^2) sqrt a sqrt b, summed: <= 2.0000002 u by
+// Cauchy-Schwarz (sum sqrt a sqrt b <= sqrt(sum a sum b) <= 1); each of the 360 multiply-accumulates is charged 2u (product,
+// sum) of a partial sum that never exceeds sum ra rb <= 1 + 2u: 720 u (1 + 722 u).  Together 722.04 u = 4.3037e-5; products
+// flushed as denormals (< 1.2e-38 each) and the float64 epilogue (3 x 2^-53) vanish in the slack of the constant below.
+#include <limits.h>
+
+#include <algorithm>
+
+#include "pm_common.h"
+
+#define PM_HELLINGER_DELTA 4.31e-5
+
+namespace pm {
+
+constexpr int HL_BM = 64;                        // moving rows per workgroup = fixed rows per tile
+constexpr int HL_KC = 40;                        // bins per LDS stage
+constexpr int HL_NCH = PM_NBINS / HL_KC;         // 9 stages per tile
+constexpr int HL_TILE = PM_NBINS * HL_BM;        // floats of one 64-row block
+constexpr int HL_STAGE = HL_KC * HL_BM;          // floats of one stage (640 float4)
+constexpr int HL_CAP = 80;                       // candidate slots per row
+constexpr int HL_KMAX = 64;
+constexpr int HL_THREADS = 256;
+constexpr int HL_SMAX = 256;                     // column splits per (row block, frame)
+constexpr int HL_SPLIT_ROWS = 512 * HL_BM;       // rows x splits never exceeds this (workspace of the partial lists)
+static_assert(HL_KC % 2 == 0 && HL_NCH * HL_KC == PM_NBINS && HL_CAP >= HL_KMAX + 16 && HL_CAP <= 128, "geometry");
+
+typedef float hl_f16 __attribute__((ext_vector_type(16)));
+
+__global__ void hl_clear_flag_kernel(int32_t *flag1) { flag1[0] = 0; }
+
+// sqrt-descriptors in the blocked layout + half row sums (bin order, float64, as relaxed_rowsum_kernel adds them).  One thread
+// per row of the padded cloud (n_pad: a multiple of 64), blockIdx.y = frame.  bad: what h holds for a non-finite / padding row.
+__global__ __launch_bounds__(256) void hl_prep_kernel(const double *__restrict__ sc, size_t frame_stride, int n, int n_pad,
+                                                      float *__restrict__ rt, double *__restrict__ h, double bad,
+                                                      int32_t *__restrict__ nonfinite1) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_pad) return;
+    const int f = blockIdx.y, r = i & 63;
+    const double *row = sc + (size_t)f * frame_stride + (size_t)i * PM_NBINS;
+    float *dst = rt + ((size_t)f * (n_pad / HL_BM) + i / HL_BM) * HL_TILE;
+    const double inf = __builtin_inf();
+    bool ok = i < n;
+    double s = 0.0;
+    if (ok) {
+        for (int q = 0; q < PM_NBINS; ++q) {
+            const double x = row[q];
+            ok = ok && (x >= 0.0) && (x < inf);
+            s += x;
+        }
+        ok = ok && (s < inf);
+    }
+    for (int q = 0; q < PM_NBINS; ++q) dst[q * HL_BM + ((r + 32 * (q & 1)) & 63)] = ok ? (float)sqrt(row[q]) : 0.0f;
+    h[(size_t)f * n_pad + i] = ok ? 0.5 * s : bad;
+    if (!ok && i < n) nonfinite1[0] = 1;
+}
+
+// LDS traffic between the lanes of ONE wave (its operations are processed in order; this keeps the compiler from moving them)
+__device__ __forceinline__ void hl_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+struct HlEntries {      // a lane's (at most two) entries of the row being ranked
+    float dot[2];
+    int col[2];
+    double v[2];
+    int rank[2];
+    bool valid[2];
+};
+
+// Ranks by (bound, column) of the n <= HL_CAP buffered entries of one row, by one wave: rank = number of smaller entries
+// (columns are distinct, so the ranks are a permutation of 0..n-1).  sv: HL_CAP doubles of this wave's scratch.
+__device__ __forceinline__ void hl_rank_row(const float *cd, const int32_t *cc, int n, double ha, const double *__restrict__ hBf,
+                                            double *sv, int lane, HlEntries &e) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int idx = lane + 64 * q;
+        e.valid[q] = idx < n;
+        e.dot[q] = e.valid[q] ? cd[idx] : 0.0f;
+        e.col[q] = e.valid[q] ? cc[idx] : INT_MAX;
+        e.v[q] = e.valid[q] ? (ha + hBf[e.col[q]]) - (double)e.dot[q] : __builtin_inf();
+        if (idx < HL_CAP) sv[idx] = e.v[q];
+        e.rank[q] = 0;
+    }
+    hl_wave_sync();
+    for (int j = 0; j < n; ++j) {
+        const double vj = sv[j];
+        const int cj = cc[j];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) e.rank[q] += (vj < e.v[q] || (vj == e.v[q] && cj < e.col[q])) ? 1 : 0;
+    }
+    hl_wave_sync();
+}
+
+// out_col / out_val: the final arrays [F][nA][k] when S == 1, the partial lists [F][nA][S][k] otherwise.
+__global__ __launch_bounds__(HL_THREADS) void hl_topk_kernel(const float *__restrict__ rAt, const float *__restrict__ rBt,
+                                                             const double *__restrict__ hA, const double *__restrict__ hB, int nA,
+                                                             int CT, int rb0, int S, int k, int32_t *__restrict__ out_col,
+                                                             double *__restrict__ out_val) {
+    __shared__ __attribute__((aligned(16))) float A_s[HL_TILE];
+    __shared__ __attribute__((aligned(16))) float B_s[2][HL_STAGE];
+    __shared__ float cd_s[HL_BM][HL_CAP];
+    __shared__ int32_t cc_s[HL_BM][HL_CAP];
+    __shared__ double sv_s[HL_THREADS / 64][HL_CAP];
+    __shared__ double hA_s[HL_BM], tau_s[HL_BM];
+    __shared__ int cnt_s[HL_BM];
+    __shared__ int ovf_s;
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rh = w & 1, ch = w >> 1;
+    const int rb = rb0 + (int)(blockIdx.x / (unsigned int)S), sp = (int)(blockIdx.x % (unsigned int)S), f = blockIdx.y;
+    const int t0 = (int)((long)sp * CT / S), t1 = (int)((long)(sp + 1) * CT / S);      // S <= CT: at least one tile
+    const double inf = __builtin_inf();
+    const double *hBf = hB + (size_t)f * CT * HL_BM;
+    const float4 *bt4 = (const float4 *)(rBt + (size_t)f * CT * HL_TILE);
+
+    {   // the row block, straight into LDS
+        const float4 *src = (const float4 *)(rAt + (size_t)rb * HL_TILE);
+        float4 *dst = (float4 *)A_s;
+        for (int i = tid; i < HL_TILE / 4; i += HL_THREADS) dst[i] = src[i];
+    }
+    if (tid < HL_BM) {
+        hA_s[tid] = hA[(size_t)rb * HL_BM + tid];
+        tau_s[tid] = inf;
+        cnt_s[tid] = 0;
+    }
+    if (tid == 0) ovf_s = 0;
+
+    // operand offsets of this lane inside a pair of bins (128 floats): bin parity = lane / 32, rotated by 32 on the odd bin
+    const int hi = lane >> 5, lo = lane & 31;
+    const int aoff = hi * HL_BM + ((32 * rh + lo + 32 * hi) & 63);
+    const int boff = hi * HL_BM + ((32 * ch + lo + 32 * hi) & 63);
+
+    float4 p0, p1, p2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    {
+        const float4 *src = bt4 + (size_t)t0 * (HL_TILE / 4);
+        p0 = src[tid];
+        p1 = src[tid + 256];
+        if (tid < 128) p2 = src[tid + 512];
+        float4 *dst = (float4 *)B_s[0];
+        dst[tid] = p0;
+        dst[tid + 256] = p1;
+        if (tid < 128) dst[tid + 512] = p2;
+    }
+    __syncthreads();
+
+    hl_f16 acc;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) acc[v] = 0.0f;
+    int tile = t0, c = 0, buf = 0;
+    double hb = hBf[(size_t)tile * HL_BM + 32 * ch + lo];
+    const long total = (long)(t1 - t0) * HL_NCH;
+    for (long st = 0; st < total; ++st) {
+        const bool has_next = st + 1 < total;
+        const int nc = (c + 1 == HL_NCH) ? 0 : c + 1, ntile = (c + 1 == HL_NCH) ? tile + 1 : tile;
+        if (has_next) {
+            const float4 *src = bt4 + (size_t)ntile * (HL_TILE / 4) + nc * (HL_STAGE / 4);
+            p0 = src[tid];
+            p1 = src[tid + 256];
+            if (tid < 128) p2 = src[tid + 512];
+        }
+        const float *Ab = A_s + c * HL_STAGE + aoff, *Bb = B_s[buf] + boff;
+#pragma unroll
+        for (int m = 0; m < HL_KC / 2; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ab[m * 128], Bb[m * 128], acc, 0, 0, 0);
+        if (has_next) {
+            float4 *dst = (float4 *)B_s[buf ^ 1];
+            dst[tid] = p0;
+            dst[tid + 256] = p1;
+            if (tid < 128) dst[tid + 512] = p2;
+        }
+        if (c == HL_NCH - 1) {
+            // ---- epilogue: this wave's 32 x 32 bounds against the rows' thresholds --------------------------------------------
+            const int col = tile * HL_BM + 32 * ch + lo;
+            unsigned int pending = 0;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int row = 32 * rh + 8 * (v >> 2) + 4 * hi + (v & 3);
+                const double val = (hA_s[row] + hb) - (double)acc[v];
+                if (val <= tau_s[row] && val != inf) {
+                    const int slot = atomicAdd(&cnt_s[row], 1);
+                    if (slot < HL_CAP) {
+                        cd_s[row][slot] = acc[v];
+                        cc_s[row][slot] = col;
+                    } else {
+                        pending |= 1u << v;
+                        ovf_s = 1;
+                    }
+                }
+            }
+            __syncthreads();
+            while (ovf_s != 0) {         // (uniform: read between two barriers)
+                __syncthreads();
+                if (tid == 0) ovf_s = 0;
+                for (int r = w; r < HL_BM; r += HL_THREADS / 64) {
+                    if (__builtin_amdgcn_readfirstlane(cnt_s[r]) < HL_CAP) continue;
+                    HlEntries e;
+                    hl_rank_row(cd_s[r], cc_s[r], HL_CAP, hA_s[r], hBf, sv_s[w], lane, e);
+#pragma unroll
+                    for (int q = 0; q < 2; ++q)
+                        if (e.valid[q] && e.rank[q] < k) {
+                            cd_s[r][e.rank[q]] = e.dot[q];
+                            cc_s[r][e.rank[q]] = e.col[q];
+                            if (e.rank[q] == k - 1) tau_s[r] = e.v[q];
+                        }
+                    if (lane == 0) cnt_s[r] = k;
+                    hl_wave_sync();
+                }
+                __syncthreads();
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    if (!(pending & (1u << v))) continue;
+                    const int row = 32 * rh + 8 * (v >> 2) + 4 * hi + (v & 3);
+                    const double val = (hA_s[row] + hb) - (double)acc[v];
+                    bool done = true;
+                    if (val <= tau_s[row]) {
+                        const int slot = atomicAdd(&cnt_s[row], 1);
+                        if (slot < HL_CAP) {
+                            cd_s[row][slot] = acc[v];
+                            cc_s[row][slot] = col;
+                        } else {
+                            done = false;
+                            ovf_s = 1;
+                        }
+                    }
+                    if (done) pending &= ~(1u << v);
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[v] = 0.0f;
+            if (has_next) hb = hBf[(size_t)ntile * HL_BM + 32 * ch + lo];
+        }
+        tile = ntile;
+        c = nc;
+        buf ^= 1;
+        __syncthreads();
+    }
+
+    // ---- the rows' lists, ascending by (bound, column) --------------------------------------------------------------------
+    for (int r = w; r < HL_BM; r += HL_THREADS / 64) {
+        const long row = (long)rb * HL_BM + r;
+        if (row >= nA) break;
+        const size_t base = (((size_t)f * nA + row) * S + sp) * k;
+        const double ha = hA_s[r];
+        if (ha != ha) {          // a non-finite moving row
+            for (int t = lane; t < k; t += 64) {
+                out_col[base + t] = -1;
+                out_val[base + t] = ha;
+            }
+            continue;
+        }
+        const int n = min(__builtin_amdgcn_readfirstlane(cnt_s[r]), HL_CAP);
+        HlEntries e;
+        hl_rank_row(cd_s[r], cc_s[r], n, ha, hBf, sv_s[w], lane, e);
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+            if (e.valid[q] && e.rank[q] < k) {
+                out_col[base + e.rank[q]] = e.col[q];
+                out_val[base + e.rank[q]] = e.v[q];
+            }
+        for (int t = min(n, k) + lane; t < k; t += 64) {
+            out_col[base + t] = -1;
+            out_val[base + t] = inf;
+        }
+    }
+}
+
+// The S sorted partial lists of one (frame, row) -> its k smallest by (bound, column).  One wave per row: a lane holds the
+// heads of lists lane, lane + 64, .. (S <= 256); k rounds of a wave-wide minimum, the winning list steps forward.
+__global__ __launch_bounds__(256) void hl_merge_kernel(const int32_t *__restrict__ pcol, const double *__restrict__ pval,
+                                                       const double *__restrict__ hA, int nA, int S, int k,
+                                                       int32_t *__restrict__ out_col, double *__restrict__ out_val) {
+    const int lane = threadIdx.x & 63, f = blockIdx.y;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= nA) return;
+    const size_t base = ((size_t)f * nA + row) * S * k, obase = ((size_t)f * nA + row) * k;
+    const double inf = __builtin_inf(), ha = hA[row];
+    if (ha != ha) {
+        for (int t = lane; t < k; t += 64) {
+            out_col[obase + t] = -1;
+            out_val[obase + t] = ha;
+        }
+        return;
+    }
+    int pos[4], hc[4];
+    double hv[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int l = lane + 64 * q;
+        pos[q] = 0;
+        hc[q] = l < S ? pcol[base + (size_t)l * k] : -1;
+        hv[q] = hc[q] >= 0 ? pval[base + (size_t)l * k] : inf;
+        if (hc[q] < 0) hc[q] = INT_MAX;
+    }
+    for (int t = 0; t < k; ++t) {
+        double bv = hv[0];
+        int bc = hc[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q)
+            if (hv[q] < bv || (hv[q] == bv && hc[q] < bc)) {
+                bv = hv[q];
+                bc = hc[q];
+            }
+        double mv = bv;
+        int mc = bc;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ov = __shfl_xor(mv, off, PM_WAVE);
+            const int oc = __shfl_xor(mc, off, PM_WAVE);
+            if (ov < mv || (ov == mv && oc < mc)) {
+                mv = ov;
+                mc = oc;
+            }
+        }
+        if (lane == 0) {
+            out_col[obase + t] = mc == INT_MAX ? -1 : mc;
+            out_val[obase + t] = mc == INT_MAX ? inf : mv;
+        }
+        if (mc == INT_MAX) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (hc[q] == mc) {          // (columns are distinct: exactly one head of one lane)
+                const int l = lane + 64 * q;
+                ++pos[q];
+                hc[q] = pos[q] < k ? pcol[base + (size_t)l * k + pos[q]] : -1;
+                hv[q] = hc[q] >= 0 ? pval[base + (size_t)l * k + pos[q]] : inf;
+                if (hc[q] < 0) hc[q] = INT_MAX;
+            }
+    }
+}
+
+struct HlWorkspace {
+    size_t rA, rB, hA, hB, pcol, pval, bytes;      // byte offsets
+};
+
+static HlWorkspace hl_workspace(int nA, int nB, int F, int k) {
+    const size_t RB = ((size_t)nA + HL_BM - 1) / HL_BM, CT = ((size_t)nB + HL_BM - 1) / HL_BM;
+    const size_t P = std::min(RB * HL_BM * HL_SMAX, (size_t)HL_SPLIT_ROWS);      // rows x splits of the partial lists, per frame
+    HlWorkspace w;
+    size_t o = 0;
+    w.rA = o, o += align_up(RB * HL_TILE * sizeof(float), 256);
+    w.rB = o, o += align_up((size_t)F * CT * HL_TILE * sizeof(float), 256);
+    w.hA = o, o += align_up(RB * HL_BM * sizeof(double), 256);
+    w.hB = o, o += align_up((size_t)F * CT * HL_BM * sizeof(double), 256);
+    w.pcol = o, o += align_up((size_t)F * P * k * sizeof(int32_t), 256);
+    w.pval = o, o += align_up((size_t)F * P * k * sizeof(double), 256);
+    w.bytes = o;
+    return w;
+}
+
+// column splits per (row block, frame): the caller's, or enough workgroups for two per CU of a 256-CU device; never more than
+// there are tiles, than HL_SMAX, or than the partial lists' workspace holds
+static int hl_splits(int split, long RB, long CT, int F) {
+    const long cap = std::min({CT, (long)HL_SMAX, std::max(1L, (long)(HL_SPLIT_ROWS / HL_BM) / RB)});
+    const long want = split > 0 ? split : (512 + RB * F - 1) / (RB * F);
+    return (int)std::max(1L, std::min(want, cap));
+}
+
+}  // namespace pm
+
+extern "C" size_t pm_hellinger_topk_workspace(int nA, int nB, int n_frames, int k) {
+    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 || k > pm::HL_KMAX) return 0;
+    return pm::hl_workspace(nA, nB, n_frames, k).bytes;
+}
+
+extern "C" int pm_hellinger_delta(double *delta1_host) {
+    if (!delta1_host) return PM_ERR_INVALID_ARG;
+    *delta1_host = PM_HELLINGER_DELTA;
+    return PM_OK;
+}
+
+extern "C" int pm_hellinger_topk(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames, int k,
+                                 int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1, void *ws, size_t ws_bytes,
+                                 void *stream) {
+    using namespace pm;
+    if (!scA || !scB || !out_col || !out_bound || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 ||
+        k > HL_KMAX || split < 0 || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
+        return PM_ERR_INVALID_ARG;
+    const HlWorkspace L = hl_workspace(nA, nB, n_frames, k);
+    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)ws;
+    float *rA = (float *)(base + L.rA), *rB = (float *)(base + L.rB);
+    double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
+    int32_t *pcol = (int32_t *)(base + L.pcol);
+    double *pval = (double *)(base + L.pval);
+    const long RB = ((long)nA + HL_BM - 1) / HL_BM, CT = ((long)nB + HL_BM - 1) / HL_BM;
+    const int S = hl_splits(split, RB, CT, n_frames);
+
+    hl_clear_flag_kernel<<<1, 1, 0, s>>>(nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((RB * HL_BM + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, (int)(RB * HL_BM), rA, hA,
+                                                                                    __builtin_nan(""), nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((CT * HL_BM + 255) / 256), n_frames), 256, 0, s>>>(scB, frame_stride, nB, (int)(CT * HL_BM), rB,
+                                                                                           hB, __builtin_inf(), nonfinite1);
+    // one launch stays under 2^32 work-items: bands of row blocks, as pm_chi2.hip's launchers cut theirs
+    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * n_frames));
+    for (long b0 = 0; b0 < RB; b0 += band) {
+        const long nb = std::min(band, RB - b0);
+        hl_topk_kernel<<<dim3((unsigned int)(nb * S), n_frames), HL_THREADS, 0, s>>>(rA, rB, hA, hB, nA, (int)CT, (int)b0, S, k,
+                                                                                    S == 1 ? out_col : pcol, S == 1 ? out_bound : pval);
+    }
+    if (S > 1)
+        hl_merge_kernel<<<dim3((unsigned int)((nA + 3) / 4), n_frames), 256, 0, s>>>(pcol, pval, hA, nA, S, k, out_col, out_bound);
+    return launch_status();
+}

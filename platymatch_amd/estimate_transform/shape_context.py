@@ -211,6 +211,34 @@ def unary_distance_matrices(unary_moving, unary_fixed, out=None):
     return U if (nat.is_torch(unary_moving[0]) or out is not None) else U.cpu().numpy()
 
 
+def unary_distance_candidates(sc_moving, unary_fixed, k=16):
+    """Per moving nucleus the k fixed nuclei that can be cheapest, WITHOUT building a cost matrix: the Hellinger lower bound
+    0.5 (sum a + sum b) - sum sqrt(a) sqrt(b) <= get_unary_distance(a, b), as a float32 GEMM on the matrix cores fused with a
+    per-row top-k (K.hellinger_topk).  sc_moving: ONE of get_unary(..., 'moving')'s arrays [N, 360]; unary_fixed: the tuple (or
+    stacked tensor) get_unary(..., 'fixed') returned, or a single [M, 360] array.  NumPy or torch in, the same kind out.
+    -> (cols int32 [F, N, k], lower float64 [F, N, k]), ascending by (lower, column), lower = bound - K.hellinger_delta():
+      * lower[f, i, r] <= get_unary_distance(sc_moving[i], unary_fixed[f][cols[f, i, r]]) for every listed entry, and
+      * lower[f, i, -1] <= get_unary_distance(sc_moving[i], unary_fixed[f][j]) for every column j that is not listed;
+      * cols -1 with lower +inf where fewer than k columns exist; -1 with NaN for a moving row holding a NaN.
+    (For descriptor rows that sum to at most 1, as get_unary's do.)
+    With sc_moving = the moving cloud's first array, frame index f = 0..3 stands for the hypotheses U11, U12, U13, U14; with its
+    second array for U21, U22, U23, U24.  Where frames 2..4 are the phi permutations of frame 1 (K.chi2_symmetric), the twins
+    U22 / U21 / U24 / U23 consist of the same terms as U11 / U12 / U13 / U14, so the first array's lists serve both.  The lists for
+    MORE moving than fixed nuclei (the assignment then takes the fixed nuclei as its rows) come from calling this with the
+    roles swapped — the bound is symmetric in its two arguments frame for frame, and under the permutation relation every
+    pairing's bin map is an involution: unary_distance_candidates(fixed frame 1, the moving frames) lists rows of U^T."""
+    torch = nat.torch_mod()
+    a = nat.to_dev(sc_moving)
+    if _stacked(unary_fixed, len(unary_fixed)) or (nat.is_torch(unary_fixed) and unary_fixed.dim() == 2) or \
+            (isinstance(unary_fixed, np.ndarray) and unary_fixed.ndim == 2):
+        f = nat.to_dev(unary_fixed, dev=a.device)
+    else:
+        f = torch.stack([nat.to_dev(x, dev=a.device) for x in unary_fixed])
+    cols, bound = K.hellinger_topk(a.contiguous(), f.contiguous(), k=k)
+    lower = bound - K.hellinger_delta()
+    return nat.like_input(cols, sc_moving), nat.like_input(lower, sc_moving)
+
+
 def _stacked(x, k):
     return nat.is_torch(x) and x.dim() == 3 and x.shape[0] == k and x.is_cuda
 

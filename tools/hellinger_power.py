@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""Pruning power and speed of the Hellinger candidate lists (K.hellinger_topk; csrc/pm_hellinger.hip) on the bench clouds, measured
+with the product's own kernels — the two kill criteria of VERDICT.md "Next round" item 1:
+  (i)  share of rows whose MATCHED column (the exact mode's assignment) lies inside the bound's top-k of the row;
+  (ii) share of a row's columns whose bound lies below the row's 16th-smallest EXACT cost (what a per-row threshold cannot prune).
+Per pairing (U11, U12, U13, U14), for k = 16, 32, 64, plus the largest |L~ - L_float64| seen on sampled rows.
+Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel]
+  --rows R       criteria on R evenly spaced rows instead of all (50 000 nuclei: the exact matrix of R rows at a time)
+  --speed        also time hellinger_topk(k=16, four frames) against chi2_filter4(float32) + pm_lsap_row_select_f32(k=16) on the
+                 four matrices: alternating, seven repetitions each after a warm-up, HIP events around work that ends in a synchronise
+  --only-kernel  descriptors + one warm-up + one hellinger_topk call, nothing else (the subject of a rocprofv3 --kernel-trace run)
+Prints to stdout; writes nothing."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("n", nargs="?", type=int, default=20000)
+    ap.add_argument("--rows", type=int, default=0)
+    ap.add_argument("--speed", action="store_true")
+    ap.add_argument("--only-kernel", action="store_true")
+    args = ap.parse_args()
+    import torch
+    import bench
+    from platymatch_amd import _kernels as K, _native as nat, lsap as L, pipeline as P
+    from platymatch_amd.estimate_transform import perform_icp as pi
+    pi.VERBOSE = False
+    n = args.n
+    mv, fx, _ = bench.synth(n)
+    be = P.GpuBackend()
+    sc_m, sc_f, _ = P.build_descriptors(be, be.cloud(mv), be.cloud(fx))
+    a = sc_m[0].contiguous()
+    delta = K.hellinger_delta()
+    print("hellinger_power: %d x %d nuclei (bench.synth), delta = %.3g" % (n, n, delta))
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    if args.only_kernel:
+        for _ in range(2):
+            ms, _ = timed(lambda: K.hellinger_topk(a, sc_f, k=16))
+        print("hellinger_topk(k=16, 4 frames): %.2f ms = %.1f TFLOP/s of 2*360*F*N*M" % (ms, 2 * 360 * 4 * n * n / ms / 1e9))
+        return
+
+    if args.speed:
+        lib = nat.load()
+        U = torch.empty((4, n, n), dtype=torch.float32, device=a.device)
+        cols = torch.empty((n, 16), dtype=torch.int32, device=a.device)
+        costs = torch.empty((n, 16), dtype=torch.float64, device=a.device)
+        flag = torch.empty(1, dtype=torch.int32, device=a.device)
+
+        def old():
+            K.chi2_filter4(a, sc_f[0].contiguous(), out=U)
+            for t in range(4):
+                nat.check(lib.pm_lsap_row_select_f32(nat.ptr(U[t]), n, n, n, None, 16, nat.ptr(cols), nat.ptr(costs), nat.ptr(flag), nat.stream_ptr(U)))
+
+        def new():
+            K.hellinger_topk(a, sc_f, k=16)
+        old(), new()
+        t_old, t_new = [], []
+        for _ in range(7):
+            t_old.append(timed(old)[0])
+            t_new.append(timed(new)[0])
+        for name, t in (("chi2_filter4(float32) + 4 x row_select_f32(k=16)", t_old), ("hellinger_topk(k=16, 4 frames)", t_new)):
+            print("speed  %-50s median %8.2f ms  min %8.2f  max %8.2f  (7 repetitions, alternating)" % (name, np.median(t), min(t), max(t)))
+        print("speed  hellinger_topk: %.1f TFLOP/s of the algorithmic 2*360*F*N*M flop" % (2 * 360 * 4 * n * n / np.median(t_new) / 1e9))
+        del U
+
+    details = {}
+    P.estimate_transform(mv, fx, cost_mode="exact", seed=0, icp_iterations=1, ransac_trials=100, details=details)
+    rows = np.arange(n) if not args.rows else np.unique(np.linspace(0, n - 1, args.rows).astype(np.int64))
+    sym = K.chi2_symmetric(sc_m, sc_f)
+    cols_t, bound_t = K.hellinger_topk(a, sc_f, k=64)
+    cols, bound = cols_t.cpu().numpy(), bound_t.cpu().numpy()
+    worst = 0.0
+    step = 2048
+    for t in range(4):
+        r_h, c_h = details["lsa"][L.PAIRINGS[t][0]]
+        match = np.full(n, -1, np.int64)
+        match[np.asarray(r_h)] = np.asarray(c_h)
+        below, total = 0, 0
+        for r0 in range(0, len(rows), step):
+            rr = torch.as_tensor(rows[r0:r0 + step], device=a.device)
+            sub = sc_m[:, rr].contiguous()
+            C = K.chi2_cost_pair(sub, sc_f, t, sym)[0]                        # the exact natural-order matrix of these rows
+            c16 = torch.kthvalue(C, 16, dim=1).values
+            ra, rb = torch.sqrt(sub[0]), torch.sqrt(sc_f[t])
+            Lref = 0.5 * (sub[0].sum(1)[:, None] + sc_f[t].sum(1)[None, :]) - ra @ rb.T          # float64 on the device: the yardstick only
+            below += int((Lref < c16[:, None]).sum())
+            total += C.numel()
+            assert bool((Lref <= C + 1e-12).all()), "the bound exceeds the exact cost"
+            got = torch.gather(Lref, 1, cols_t[t, rr].long().clamp(min=0))
+            worst = max(worst, float((got - bound_t[t, rr]).abs().max()))
+        line = "pairing %d (U1%d): (ii) columns with bound below the row's 16th exact cost: %.2f %%;  (i) matched column listed:" % (t, t + 1, 100.0 * below / total)
+        for k in (16, 32, 64):
+            hit = (cols[t, rows, :k] == match[rows, None]).any(1)
+            line += "  k=%d %.2f %%" % (k, 100.0 * hit[match[rows] >= 0].mean())
+        print(line)
+    print("largest |bound - L_float64| on listed entries: %.3g (delta %.3g)" % (worst, delta))
+
+
+if __name__ == "__main__":
+    main()

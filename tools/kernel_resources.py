@@ -26,7 +26,7 @@ def census(files=None):
         with tempfile.TemporaryDirectory() as d:
             out = os.path.join(d, "k.s")
             # the compiler, target and flags of the product's own build (platymatch_amd/build.py)
-            subprocess.run([B._hipcc()] + [x for x in B.FLAGS if x != "-fPIC"] + ["-S", "--cuda-device-only", os.path.join(CSRC, f), "-o", out],
+            subprocess.run([B._hipcc()] + [x for x in B.FLAGS if x != "-fPIC"] + B.EXTRA_FLAGS.get(f, []) + ["-S", "--cuda-device-only", os.path.join(CSRC, f), "-o", out],
                            check=True, capture_output=True)
             text = open(out).read()
         meta = text[text.find("amdhsa.kernels:"):]
