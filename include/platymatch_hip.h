@@ -302,15 +302,24 @@ int pm_chi2_entries_sym(const double *sc_m1, int nM, const double *sc_f1, int nF
  * (get_shape_context's sc / sc.sum(), shape_context.py:40-43), so (a-b)^2/(a+b) is a function of two small integers.  The
  * calls recover the counts from the doubles and verify bit for bit that every value is fl(count / total); the table is filled
  * by the same operations on the same operands, so the result has the bits of pm_chi2_cost8_sym / pm_chi2_cost_pair_sym for ANY
- * input (descriptors that are not count / total, or shells with counts of 88 and more, are computed term by term). */
+ * input (descriptors that are not count / total are computed term by term; so is a shell in every 16 x 64 tile of the matrix
+ * in which one of the tile's 16 moving or 64 fixed descriptors holds a count of 94 or more in that shell: each tile decides). */
 size_t pm_chi2_sym_workspace_bytes(int nM, int nF);
 int pm_chi2_cost8_sym_ws(const double *sc_m1, int nM, const double *sc_f1, int nF, double *out, size_t ld,
                          size_t matrix_stride, void *ws, size_t ws_bytes, void *stream);
 int pm_chi2_cost_pair_sym_ws(const double *sc_m1, int nM, const double *sc_f1, int nF, int pairing, double *out2, size_t ld,
                              size_t matrix_stride, void *ws, size_t ws_bytes, void *stream);
 /* Report (benchmarks, tests): tabled30[g] = 1 if the last *_ws launch on this workspace took shell g = 6*ring + theta sector from
- * the table, table_size = its side.  Copies 300 bytes to the host and synchronises the stream. */
+ * the table IN EVERY TILE (the shell's largest count over both clouds is below the table's side), table_size = its side.  Tiles
+ * may table further shells on their own: pm_chi2_sym_ws_report counts them.  Copies 300 bytes to the host and synchronises the
+ * stream. */
 int pm_chi2_sym_table_info(const void *ws, int32_t *tabled30, int32_t *table_size, void *stream);
+/* pm_chi2_cost8_sym_ws (pairing = -1: out = eight matrices) or pm_chi2_cost_pair_sym_ws (pairing = 0..3: out = two) with a
+ * per-shell count of the tiles that served the shell from the table: tiles_tabled30 (device, 30 x uint32, may be NULL) is
+ * INCREMENTED — the caller clears it — once per 16-row x 64-column tile and shell; the launch has ceil(nM/16) * ceil(nF/64)
+ * tiles.  Same matrices, same bits. */
+int pm_chi2_sym_ws_report(const double *sc_m1, int nM, const double *sc_f1, int nF, int pairing, double *out, size_t ld,
+                          size_t matrix_stride, void *ws, size_t ws_bytes, uint32_t *tiles_tabled30, void *stream);
 
 /* np.argmin(U_h, axis=1) for n_mat stacked cost matrices (U_h = U + h*matrix_stride, rows x cols, leading
  * dimension ld): idx[h*rows + i] = first index of the minimum of row i, or of the first NaN if the row holds one

@@ -326,6 +326,25 @@ def chi2_cost8_frame1(sc_m1, sc_f1, out=None, info=None):
     return out
 
 
+def chi2_frame1_tile_report(sc_m1, sc_f1, pairing=-1):
+    """What the tiles of the half-cost kernel did (tools, tests): chi2_cost8_frame1 (pairing -1 -> [8, nM, nF]) or one pairing's two
+    matrices (pairing 0..3 -> [2, nM, nF], natural order first) through pm_chi2_sym_ws_report -> (matrices, tabled, tiles):
+    tabled[g] = how many of the `tiles` = ceil(nM / 16) * ceil(nF / 64) tiles served shell g from the term table (int32 [30])."""
+    torch = _t()
+    a, b = _desc(sc_m1, "sc_m1"), _desc(sc_f1, "sc_f1")
+    nM, nF = a.shape[0], b.shape[0]
+    t = int(pairing)
+    if t not in (-1, 0, 1, 2, 3):
+        raise ValueError("pairing must be -1 (all eight matrices) or 0..3")
+    out = big_empty((8 if t < 0 else 2, nM, nF), torch.float64, a.device)
+    lib = nat.load()
+    ws = _sym_workspace(lib, nM, nF, a.device)
+    tabled = torch.zeros(30, dtype=torch.int32, device=a.device)
+    check(lib.pm_chi2_sym_ws_report(ptr(a), nM, ptr(b), nF, t, ptr(out), out.stride(1), out.stride(0), ptr(ws), ws.numel(), ptr(tabled),
+                                    nat.stream_ptr()))
+    return out, tabled, ((nM + 15) // 16) * ((nF + 63) // 64)
+
+
 def chi2_cost8_relaxed(sc_m1, sc_f1, out=None, variant=1):
     """OPT-IN EXPERIMENT (never the default): the eight matrices from the frame-1 descriptors in relaxed float64 arithmetic —
     U = 0.5 (sum a + sum b) - 2 sum ab/(a+b), reciprocal with one Newton step, sums in any order, the twins identical

@@ -109,6 +109,8 @@ SIGNATURES = {
     "pm_chi2_cost8_sym_ws": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_size_t, _c_size_t, _c_void_p, _c_size_t, _c_void_p]),
     "pm_chi2_cost_pair_sym_ws": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size_t, _c_size_t, _c_void_p,
                                           _c_size_t, _c_void_p]),
+    "pm_chi2_sym_ws_report": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size_t, _c_size_t, _c_void_p,
+                                       _c_size_t, _c_void_p, _c_void_p]),
     "pm_ransac_affine": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_int,
                                   _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "pm_ransac_draw": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_uint64, ctypes.c_uint32, _c_void_p, _c_void_p]),

@@ -186,14 +186,18 @@ int chi2_launch(const Chi2Args<NFA, NFB> &args, int nA, int nB, double *out, siz
 // Term table (TL > 0).  A descriptor value is count / total (get_shape_context: sc / sc.sum(), shape_context.py:40-43), so a
 // term (a-b)^2/(a+b) is a function of two small integers and the two totals.  counts_* below recover the counts from the
 // doubles and VERIFY, bit for bit, that every value is fl(count / total) — nothing is assumed; one failure and the launch
-// computes every term as before.  Where all counts of a shell (both clouds) are below TL, the shell's 48 terms per pair
-// come out of a TL x TL table in LDS, filled at the start of the workgroup by the SAME operations on the SAME operands
-// (fl(ca/totA), fl(cb/totB) or 1e-300, div_pos) — identical bits by construction — at one ds_read_b64 + one address add per
-// term instead of a 13-slot division.  The moving count is wave-uniform (a scalar row offset), the fixed count per lane,
-// so a wave reads one table row: lanes with equal counts broadcast, counts 32 apart conflict.  Shells with larger counts
-// (the outer ones of a large cloud) are computed.
+// computes every term as before.  Where all counts of a shell are below TL IN THE 16 ROWS AND 64 COLUMNS OF A TILE, that tile
+// takes the shell's 48 terms per pair out of a TL x TL table in LDS, filled at the start of the workgroup by the SAME operations
+// on the SAME operands (fl(ca/totA), fl(cb/totB) or 1e-300, div_pos) — identical bits by construction — at one ds_read_b64 + one
+// address add per term instead of a 13-slot division.  The moving count is wave-uniform (a scalar row offset), the fixed count
+// per lane, so a wave reads one table row: lanes with equal counts broadcast, counts 32 apart conflict.  The choice is the
+// workgroup's own: shells whose launch-wide maximum (meta->maxc) is below TL are tabled everywhere; for the others the workgroup
+// scans the count bytes of its 80 rows (12 bytes per row and shell, 2 400 groups over 256 threads) and computes a shell only if
+// one of them reaches TL — a few hundred rows with 94..117 neighbours in a bin no longer cost all 2.4 M tiles of a 50k build
+// that shell (tools/tile_table_census.py, profiles/tile_table_census.txt).  A tile with no eligible shell skips the table fill.
+// meta->maxc and pm_chi2_sym_table_info keep the launch-wide view; pm_chi2_sym_ws_report counts the tiles that tabled each shell.
 constexpr int CH_NSHELL = CH_STAGES;
-constexpr int CH_TL = 94;              // 94 x 94 doubles + the staging tiles = 79 392 B: two workgroups per CU (160 KiB), as the registers allow
+constexpr int CH_TL = 94;              // 94 x 94 doubles + the staging tiles + the tile's mask word = 79 400 B: two workgroups per CU (160 KiB), as the registers allow
 struct SymMeta {
     unsigned long long minbits[2];     // smallest positive descriptor value of each cloud (bit pattern; +inf if none)
     double tot[2];                     // its reciprocal rounded to an integer: the candidate total
@@ -228,7 +232,8 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
                                                                  const unsigned char *__restrict__ cntB = nullptr,
                                                                  const SymMeta *__restrict__ meta = nullptr,
                                                                  const double *__restrict__ sumA = nullptr,
-                                                                 const double *__restrict__ sumB = nullptr) {
+                                                                 const double *__restrict__ sumB = nullptr,
+                                                                 unsigned int *__restrict__ report = nullptr) {
     constexpr int SY_TI = 4 * SY_RI;      // rows per tile
     __shared__ __attribute__((aligned(16))) double A_s[SY_TI][CH_K];
     __shared__ __attribute__((aligned(16))) double B_s[CH_TJ][CH_BPITCH];
@@ -251,14 +256,11 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
 #pragma unroll
         for (int h = 0; h < NACC; ++h) acc[r][h] = 0.0;
 
-    unsigned int tabmask = 0;             // shells served from the table (uniform)
+    unsigned int tabmask = 0;             // shells this TILE serves from the table (uniform over the workgroup)
     if constexpr (TL > 0) {
-        if (meta->bad == 0) {
-            for (int g = 0; g < CH_STAGES; ++g)
-                if (meta->maxc[0][g] < TL && meta->maxc[1][g] < TL) tabmask |= 1u << g;
-        }
-        tabmask = __builtin_amdgcn_readfirstlane(tabmask);
-        if (tabmask) {
+        static_assert(TL <= 128 && CH_STAGES < 32, "the packed byte test below; one mask bit per shell");
+        __shared__ unsigned int over_s;   // shells in which a row or a column of this tile holds a count >= TL
+        auto fill = [&]() {
             const double totA = meta->tot[0], totB = meta->tot[1];
             for (int e = tid; e < TL * TL; e += CH_THREADS) {
                 const int ca = e / TL, cb = e - ca * TL;
@@ -266,8 +268,55 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
                 const double df = a - b;
                 tab[e] = RELAX ? (a * b) * relaxed_recip(a + b) : div_pos(df * df, a + b);
             }
-            __syncthreads();
+        };
+        if (meta->bad == 0) {
+            unsigned int wide = 0;        // shells below TL in every row of both clouds: tabled in every tile
+            for (int g = 0; g < CH_STAGES; ++g)
+                if (meta->maxc[0][g] < TL && meta->maxc[1][g] < TL) wide |= 1u << g;
+            wide = __builtin_amdgcn_readfirstlane(wide);
+            constexpr unsigned int ALL = (1u << CH_STAGES) - 1u;
+            if (RELAX || wide == ALL) {
+                tabmask = wide;           // (relaxed build: table and computed terms differ in rounding; it keeps the launch-wide rule)
+                if (tabmask) fill();
+            } else {
+                // the other shells: the (row, shell) groups of twelve count bytes of the tile's SY_TI rows and CH_TJ columns, at the
+                // clamped indices the lookups use.  All of a thread's groups are fetched at once (no branch between the loads: the
+                // workgroup waits ONE L2 round trip, and the table fill runs under it where the launch-wide shells need the table
+                // anyway); a group past the end repeats the last one.  A byte c has c >= TL iff bit 7 of ((c & 127) + 128 - TL) | c.
+                constexpr int NGRP = (SY_TI + CH_TJ) * CH_STAGES, NIT = (NGRP + CH_THREADS - 1) / CH_THREADS;
+                unsigned int w[NIT][3];
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int e = min(tid + it * CH_THREADS, NGRP - 1);
+                    const int row = e / CH_STAGES, g = e - row * CH_STAGES;
+                    const unsigned char *c = (row < SY_TI) ? cntA + (size_t)min(i0 + row, nA - 1) * PM_NBINS
+                                                           : cntB + (size_t)min(j0 + row - SY_TI, nB - 1) * PM_NBINS;
+                    const unsigned int *p = reinterpret_cast<const unsigned int *>(c) + g * 3;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) w[it][k] = p[k];
+                }
+                if (tid == 0) over_s = 0u;
+                if (wide) fill();
+                __syncthreads();
+                unsigned int over = 0;
+#pragma unroll
+                for (int it = 0; it < NIT; ++it) {
+                    const int e = min(tid + it * CH_THREADS, NGRP - 1);
+                    const int g = e % CH_STAGES;
+                    unsigned int hi = 0;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) hi |= ((w[it][k] & 0x7f7f7f7fu) + 0x01010101u * (unsigned int)(128 - TL)) | w[it][k];
+                    if (hi & 0x80808080u) over |= 1u << g;
+                }
+                if (over) atomicOr(&over_s, over);
+                __syncthreads();
+                tabmask = __builtin_amdgcn_readfirstlane(ALL & ~over_s);
+                if (!wide && tabmask) fill();          // (wide is part of every tile's mask: otherwise the table is filled already)
+            }
         }
+        tabmask = __builtin_amdgcn_readfirstlane(tabmask);
+        if (report && tid < CH_STAGES && ((tabmask >> tid) & 1u)) atomicAdd(&report[tid], 1u);
+        if (tabmask) __syncthreads();
     }
 
     // counts of the next tabled shell, fetched one tabled shell ahead (an L2 round trip is about as long as a tabled shell):
@@ -667,7 +716,7 @@ namespace pm {
 template <int RI, int MINW, int TSEL = -1, int TL = 0, bool RELAX = false>
 int chi2_sym_launch(const double *sc_m1, int nM, const double *sc_f1, int nF, double *out, size_t ld, size_t mstride, hipStream_t s,
                     const unsigned char *cntA = nullptr, const unsigned char *cntB = nullptr, const SymMeta *meta = nullptr,
-                    const double *sumA = nullptr, const double *sumB = nullptr) {
+                    const double *sumA = nullptr, const double *sumB = nullptr, unsigned int *report = nullptr) {
     const long nTi = ((long)nM + 4 * RI - 1) / (4 * RI), nTj = ((long)nF + CH_TJ - 1) / CH_TJ;
     const long band = band_tile_rows(nTj);
     if (band == 0) return PM_ERR_INVALID_ARG;
@@ -679,7 +728,7 @@ int chi2_sym_launch(const double *sc_m1, int nM, const double *sc_f1, int nF, do
         const unsigned int nblocks = (unsigned int)(tiles * nTj);
         chi2_sym_kernel<RI, MINW, TSEL, TL, RELAX><<<nblocks, CH_THREADS, 0, s>>>(
             sc_m1 + (size_t)r0 * PM_NBINS, rows, sc_f1, nF, out + (size_t)r0 * ld, ld, mstride, (int)tiles, nblocks,
-            cntA ? cntA + (size_t)r0 * PM_NBINS : nullptr, cntB, meta, sumA ? sumA + r0 : nullptr, sumB);
+            cntA ? cntA + (size_t)r0 * PM_NBINS : nullptr, cntB, meta, sumA ? sumA + r0 : nullptr, sumB, report);
     }
     return launch_status();
 }
@@ -943,22 +992,33 @@ extern "C" int pm_chi2_cost8_sym_ws(const double *sc_m1, int nM, const double *s
     return pm_chi2_cost8_sym_ws_variant(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, ws, ws_bytes, 1, stream);
 }
 
-extern "C" int pm_chi2_cost_pair_sym_ws(const double *sc_m1, int nM, const double *sc_f1, int nF, int pairing, double *out2, size_t ld,
-                                        size_t matrix_stride, void *ws, size_t ws_bytes, void *stream) {
-    if (!sc_m1 || !sc_f1 || !out2 || nM <= 0 || nF <= 0 || ld < (size_t)nF || matrix_stride < (size_t)nM * ld)
+// The two *_ws builds with a report of what the tiles did: pairing -1 = pm_chi2_cost8_sym_ws, 0..3 = pm_chi2_cost_pair_sym_ws.
+// tiles_tabled30 (device, 30 counters, may be NULL): counter g is raised by one for every 16 x 64 tile that took shell g from the
+// table — ADDED to what the counters hold (the caller clears them), over all bands of the launch.
+extern "C" int pm_chi2_sym_ws_report(const double *sc_m1, int nM, const double *sc_f1, int nF, int pairing, double *out, size_t ld,
+                                     size_t matrix_stride, void *ws, size_t ws_bytes, uint32_t *tiles_tabled30, void *stream) {
+    if (!sc_m1 || !sc_f1 || !out || nM <= 0 || nF <= 0 || ld < (size_t)nF || matrix_stride < (size_t)nM * ld)
         return PM_ERR_INVALID_ARG;
-    if (((uintptr_t)sc_f1 & 15) != 0 || ((uintptr_t)sc_m1 & 15) != 0) return PM_ERR_INVALID_ARG;
-    if (pairing < 0 || pairing > 3) return PM_ERR_INVALID_ARG;
+    if (((uintptr_t)sc_f1 & 15) != 0 || ((uintptr_t)sc_m1 & 15) != 0 || ((uintptr_t)tiles_tabled30 & 3) != 0) return PM_ERR_INVALID_ARG;
+    if (pairing < -1 || pairing > 3) return PM_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     pm::SymWs w;
     const int rc = pm::sym_prepare(sc_m1, nM, sc_f1, nF, ws, ws_bytes, s, w);
     if (rc != PM_OK) return rc;
+    unsigned int *rep = tiles_tabled30;
     switch (pairing) {
-        case 0: return pm::chi2_sym_launch<4, 2, 0, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out2, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
-        case 1: return pm::chi2_sym_launch<4, 2, 1, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out2, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
-        case 2: return pm::chi2_sym_launch<4, 2, 2, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out2, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
-        default: return pm::chi2_sym_launch<4, 2, 3, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out2, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
+        case -1: return pm::chi2_sym_launch<4, 2, -1, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
+        case 0: return pm::chi2_sym_launch<4, 2, 0, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
+        case 1: return pm::chi2_sym_launch<4, 2, 1, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
+        case 2: return pm::chi2_sym_launch<4, 2, 2, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
+        default: return pm::chi2_sym_launch<4, 2, 3, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
     }
+}
+
+extern "C" int pm_chi2_cost_pair_sym_ws(const double *sc_m1, int nM, const double *sc_f1, int nF, int pairing, double *out2, size_t ld,
+                                        size_t matrix_stride, void *ws, size_t ws_bytes, void *stream) {
+    if (pairing < 0 || pairing > 3) return PM_ERR_INVALID_ARG;
+    return pm_chi2_sym_ws_report(sc_m1, nM, sc_f1, nF, pairing, out2, ld, matrix_stride, ws, ws_bytes, nullptr, stream);
 }
 
 extern "C" int pm_chi2_cost_pair_sym(const double *sc_m1, int nM, const double *sc_f1, int nF, int pairing, double *out2, size_t ld,
