@@ -286,6 +286,25 @@ int pm_hellinger_topk(const double *scA, int nA, const double *scB, int nB, size
                       void *stream);
 int pm_hellinger_delta(double *delta1_host);
 
+/* THRESHOLD LISTING from the same bound (hl_list_kernel), the matrix-free form of a pricing / certificate pass: entry (f, i, j) is
+ * listed iff  (bound - v[f][j]) - u[f][i] <= tau  and  j != skip[f][i],  bound = (hA_i + hB_j) - (double)dot in float64, in that
+ * order — the bits pm_hellinger_topk reports for the same entry, for any split.
+ *   scA, scB, frame_stride, n_frames, split: as above;  u [n_frames][nA] row duals, v [n_frames][nB] column prices (device);
+ *   skip [n_frames][nA]: a column per row that is never listed (the matched one), or -1; may be NULL;  tau: not NaN, +inf lists
+ *   every entry of finite rows;
+ *   out_rc [n_frames][cap][2] (row, column), out_bound [n_frames][cap] (the bound, NOT the reduced value), in no particular
+ *   order inside a frame;  count[f]: the TRUE number of qualifying entries of frame f (saturating at INT_MAX): where it exceeds
+ *   cap, only cap of them were written and the list is incomplete.  Entries of a non-finite or padding row of either side and
+ *   entries with a NaN dual are never listed.  nonfinite1 as above.
+ * CONTRACT, for descriptor rows with sum <= 1 and delta = pm_hellinger_delta: every entry that is NOT listed and not skipped,
+ * with finite rows and duals, has C(i, j) - u_i - v_j > tau - delta (the float64 rounding of the two subtractions lies in the
+ * slack of the constant for |u|, |v| <= 1e6).  ws: pm_hellinger_list_workspace bytes, 16-byte aligned device memory. */
+size_t pm_hellinger_list_workspace(int nA, int nB, int n_frames);
+int pm_hellinger_list(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames,
+                      const double *u, const double *v, const int32_t *skip, double tau, int split,
+                      int32_t *out_rc, double *out_bound, int cap, int32_t *count, int32_t *nonfinite1,
+                      void *ws, size_t ws_bytes, void *stream);
+
 /* Listed entries of one pairing's two EXACT matrices (the bits of pm_chi2_cost_pair_sym's): out_natural[e], out_rolled[e] =
  * entry (rows[e], cols[e]) of the natural-order matrix (U11, U12, U13, U14 for pairing 0..3) and of its rolled-order twin (U22,
  * U21, U24, U23).  rows / cols / outputs: device, n_entries each; an index out of range yields NaN in both outputs.  What turns

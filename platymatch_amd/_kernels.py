@@ -441,6 +441,63 @@ def hellinger_topk(sc_a, sc_b, k=16, split=0, info=None):
     return cols, bound
 
 
+def _hellinger_list_raw(a, sc_b, u, v, skip, tau, split, rc, bound, cap, count, flag):
+    """One pm_hellinger_list call on prepared tensors (the outputs may be longer than cap: the tests' guard tails)."""
+    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
+    N, M = a.shape[0], sc_b.shape[-2]
+    lib = nat.load()
+    ws = nat.workspace(lib.pm_hellinger_list_workspace(N, M, F), a.device)
+    check(lib.pm_hellinger_list(ptr(a), N, ptr(sc_b), M, M * NBINS, F, ptr(u), ptr(v), ptr(skip), float(tau), int(split), ptr(rc),
+                                ptr(bound), int(cap), ptr(count), ptr(flag), ptr(ws), ws.numel(), nat.stream_ptr()))
+
+
+def hellinger_list(sc_a, sc_b, u, v, tau, skip=None, cap=None, split=0, info=None):
+    """Every entry whose Hellinger lower bound, reduced by the duals, is at most tau — the listing pass of a pricing round or a
+    certificate without a matrix (pm_hellinger_list; csrc/pm_hellinger.hip: hl_list_kernel).  sc_a [N, 360], sc_b [F, M, 360] (or
+    [M, 360]: F = 1) as for hellinger_topk; u [F, N] row duals, v [F, M] column prices (float64 GPU tensors), skip [F, N] int32: a
+    column per row that is never listed (-1: none).  Entry (f, i, j) is listed iff (bound - v[f, j]) - u[f, i] <= tau and
+    j != skip[f, i]; bound carries the bits hellinger_topk reports for the entry, for any split.
+    -> a list of F tuples (rows int32, cols int32, bound float64), GPU tensors sorted by (row, column); None in the slot of a frame
+    whose count exceeds cap (default 64 * M): an incomplete list never passes for complete.  Every entry NOT listed (finite rows
+    and duals, not skipped) has exact cost - u - v > tau - hellinger_delta().  info (dict): receives 'count' (per frame, the true
+    numbers) and 'nonfinite'.  Synchronises (the counts are read back)."""
+    torch = _t()
+    a = _desc(sc_a, "sc_a")
+    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
+            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
+        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
+    _here(sc_b, "sc_b")
+    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
+    N, M = a.shape[0], sc_b.shape[-2]
+    u, v = _vec(u, F * N, "u"), _vec(v, F * M, "v")
+    _here(u, "u"), _here(v, "v")
+    if skip is not None:
+        if not (nat.is_torch(skip) and skip.is_cuda and skip.dtype == torch.int32 and skip.is_contiguous() and skip.numel() == F * N):
+            raise ValueError("skip must be a contiguous int32 GPU tensor with %d elements" % (F * N))
+        _here(skip, "skip")
+    tau, split = float(tau), int(split)
+    cap = 64 * M if cap is None else int(cap)
+    if tau != tau or split < 0 or not 1 <= cap < 2 ** 31 // 2:
+        raise ValueError("tau must not be NaN, split >= 0 (0 = automatic), cap 1..2^30 - 1")
+    rc = torch.empty((F, cap, 2), dtype=torch.int32, device=a.device)
+    bound = torch.empty((F, cap), dtype=torch.float64, device=a.device)
+    count = torch.empty(F, dtype=torch.int32, device=a.device)
+    flag = torch.empty(1, dtype=torch.int32, device=a.device)
+    _hellinger_list_raw(a, sc_b, u, v, skip, tau, split, rc, bound, cap, count, flag)
+    counts = [int(c) for c in count.tolist()]
+    if info is not None:
+        info["count"], info["nonfinite"] = counts, int(flag.item())
+    out = []
+    for f, n in enumerate(counts):
+        if n > cap:
+            out.append(None)
+            continue
+        rows, cols = rc[f, :n, 0].long(), rc[f, :n, 1].long()
+        order = torch.argsort(rows * M + cols)
+        out.append((rows[order].int(), cols[order].int(), bound[f, :n][order]))
+    return out
+
+
 def hellinger_delta():
     """Absolute error bound of hellinger_topk's bounds against the float64 Hellinger bound, for descriptor rows that sum to at
     most 1 (csrc/pm_hellinger.hip: PM_HELLINGER_DELTA)."""

@@ -394,7 +394,254 @@ static int hl_splits(int split, long RB, long CT, int F) {
     return (int)std::max(1L, std::min(want, cap));
 }
 
+// ---- threshold listing: every entry whose bound, reduced by the duals, is at most tau ---------------------------------------
+// hl_list_kernel answers the solver's third question (lsap.FilteredMatrix.certificate / threshold_select) without a matrix:
+// entry (f, i, j) is listed iff  (L~ - v[f][j]) - u[f][i] <= tau  and  j != skip[f][i],  L~ = (hA_i + hB_j) - (double)dot — the
+// same bits hl_topk_kernel reports for the entry (same instruction, same operands, bins 0..359 in order).  There is no per-row
+// state, so nothing is resident:
+//   - a 256-thread workgroup owns a PANEL of 128 moving rows (two blocks of the layout above) and a range of 128-column tiles
+//     of one fixed frame; both operands stream through two LDS stages of HLL_KC = 20 bins: a stage is 2 x (2 blocks x 5 120
+//     contiguous bytes) = 20 KB, global -> registers -> LDS as six 16-byte copies per thread, issued before the stage's MFMAs
+//     and stored after them: one barrier per stage of 40 MFMAs per wave;
+//   - wave w owns the 64 x 64 sub-tile (row block w & 1, column block w >> 1) as FOUR 32 x 32 accumulators: per pair of bins two
+//     A reads and two B reads (ds_read_b32, 64 distinct banks each by the odd-bin rotation) feed four independent
+//     v_mfma_f32_32x32x2f32 chains — hl_topk_kernel has one chain of 180;
+//   - LDS 2 x 20 480 + 2 560 (the panel's hA, u, skip) = 43 520 B: three workgroups per CU; no scratch;
+//   - epilogue in registers: 64 entries per lane per tile in float64, a 64-bit mask of the qualifying ones.  Survivors are rare,
+//     so a wave whose ballot is empty goes on; otherwise ONE atomicAdd per wave per tile (lane 0, after a wave prefix sum of the
+//     lanes' counts) on the frame's 64-bit counter reserves the slots, and each lane writes its entries that fall below cap.
+// The column tiles are split over S workgroups per (panel, frame) as in hl_splits; an entry is computed whole by one workgroup,
+// so the listed set and its bits do not depend on S.  hl_list_finish_kernel turns the 64-bit counters into count[F] (saturated).
+// Measured (profiles/hellinger_list_20k.txt): 20 000 x 20 000 x 4 frames at 16 entries per row, the whole call with its sort by
+// (row, column): 11.5 ms against hl_topk_kernel's call at 22.2 ms.
+constexpr int HLL_BM = 2 * HL_BM;                 // rows per panel = columns per tile
+constexpr int HLL_KC = 20;                        // bins per LDS stage
+constexpr int HLL_NCH = PM_NBINS / HLL_KC;        // 18 stages per tile
+constexpr int HLL_HALF = HLL_KC * HL_BM;          // floats of one block's part of a stage (320 float4)
+constexpr int HLL_STAGE = 2 * HLL_HALF;           // floats of one operand's stage (640 float4)
+static_assert(HLL_KC % 2 == 0 && HLL_NCH * HLL_KC == PM_NBINS && HLL_STAGE / 4 == 2 * HL_THREADS + HL_THREADS / 2, "geometry");
+
+__global__ void hl_list_clear_kernel(unsigned long long *cnt, int F, int32_t *flag1) {
+    if ((int)threadIdx.x < F) cnt[threadIdx.x] = 0ull;
+    if (threadIdx.x == 0) flag1[0] = 0;
+}
+
+__global__ void hl_list_finish_kernel(const unsigned long long *cnt, int F, int32_t *count) {
+    if ((int)threadIdx.x < F) count[threadIdx.x] = (int32_t)min(cnt[threadIdx.x], (unsigned long long)INT_MAX);
+}
+
+__global__ __launch_bounds__(HL_THREADS, 2) void hl_list_kernel(const float *__restrict__ rAt, const float *__restrict__ rBt,
+                                                             const double *__restrict__ hA, const double *__restrict__ hB,
+                                                             const double *__restrict__ u, const double *__restrict__ v,
+                                                             const int32_t *__restrict__ skip, double tau, int nA, int nB, int CT,
+                                                             int pb0, int S, int cap, int32_t *__restrict__ out_rc,
+                                                             double *__restrict__ out_bound, unsigned long long *__restrict__ cnt) {
+    __shared__ __attribute__((aligned(16))) float A_s[2][HLL_STAGE];
+    __shared__ __attribute__((aligned(16))) float B_s[2][HLL_STAGE];
+    __shared__ double hA_s[HLL_BM], u_s[HLL_BM];
+    __shared__ int32_t skip_s[HLL_BM];
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rh = w & 1, ch = w >> 1;
+    const int pb = pb0 + (int)(blockIdx.x / (unsigned int)S), sp = (int)(blockIdx.x % (unsigned int)S), f = blockIdx.y;
+    const int t0 = (int)((long)sp * CT / S), t1 = (int)((long)(sp + 1) * CT / S);      // S <= CT: at least one tile
+    const double *hBf = hB + (size_t)f * CT * HLL_BM;
+    const double *vf = v + (size_t)f * nB;
+    const float4 *at4 = (const float4 *)(rAt + (size_t)pb * 2 * HL_TILE);
+    const float4 *bt4 = (const float4 *)(rBt + (size_t)f * CT * 2 * HL_TILE);
+
+    if (tid < HLL_BM) {
+        const long row = (long)pb * HLL_BM + tid;
+        hA_s[tid] = hA[row];                                                            // (padded: NaN past the cloud's end)
+        u_s[tid] = row < nA ? u[(size_t)f * nA + row] : 0.0;
+        skip_s[tid] = (skip && row < nA) ? skip[(size_t)f * nA + row] : -1;
+    }
+
+    // a stage of one operand is 640 float4: 320 of the panel's first block, 320 of its second; this thread copies three of them
+    // (the third only in the lower half of the workgroup), from the same offsets of both operands
+    int so[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int j = tid + HL_THREADS * q;
+        so[q] = (j / (HLL_HALF / 4)) * (HL_TILE / 4) + j % (HLL_HALF / 4);
+    }
+    const bool third = tid < HL_THREADS / 2;
+    // operand offsets of this lane inside a pair of bins (128 floats) of its block, for the two 32-row halves
+    const int hi = lane >> 5, lo = lane & 31;
+    const int off0 = hi * HL_BM + ((lo + 32 * hi) & 63), off1 = hi * HL_BM + ((32 + lo + 32 * hi) & 63);
+
+    float4 pa0, pa1, pa2 = make_float4(0.f, 0.f, 0.f, 0.f), pb0r, pb1r, pb2r = make_float4(0.f, 0.f, 0.f, 0.f);
+    {
+        const float4 *sb = bt4 + (size_t)t0 * (2 * HL_TILE / 4);
+        pa0 = at4[so[0]], pa1 = at4[so[1]];
+        pb0r = sb[so[0]], pb1r = sb[so[1]];
+        if (third) pa2 = at4[so[2]], pb2r = sb[so[2]];
+        float4 *da = (float4 *)A_s[0], *db = (float4 *)B_s[0];
+        da[tid] = pa0, da[tid + HL_THREADS] = pa1;
+        db[tid] = pb0r, db[tid + HL_THREADS] = pb1r;
+        if (third) da[tid + 2 * HL_THREADS] = pa2, db[tid + 2 * HL_THREADS] = pb2r;
+    }
+    __syncthreads();
+
+    hl_f16 acc00, acc01, acc10, acc11;              // (row half, column half) of the wave's 64 x 64
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.0f;
+    int tile = t0, c = 0, buf = 0;
+    const long total = (long)(t1 - t0) * HLL_NCH;
+    for (long st = 0; st < total; ++st) {
+        const bool has_next = st + 1 < total;
+        const int nc = (c + 1 == HLL_NCH) ? 0 : c + 1, ntile = (c + 1 == HLL_NCH) ? tile + 1 : tile;
+        if (has_next) {
+            const float4 *sa = at4 + nc * (HLL_HALF / 4);
+            const float4 *sb = bt4 + (size_t)ntile * (2 * HL_TILE / 4) + nc * (HLL_HALF / 4);
+            pa0 = sa[so[0]], pa1 = sa[so[1]];
+            pb0r = sb[so[0]], pb1r = sb[so[1]];
+            if (third) pa2 = sa[so[2]], pb2r = sb[so[2]];
+        }
+        const float *Ab = A_s[buf] + rh * HLL_HALF, *Bb = B_s[buf] + ch * HLL_HALF;
+#pragma unroll
+        for (int m = 0; m < HLL_KC / 2; ++m) {
+            const float a0 = Ab[m * 128 + off0], a1 = Ab[m * 128 + off1], b0 = Bb[m * 128 + off0], b1 = Bb[m * 128 + off1];
+            acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
+            acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
+            acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
+            acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
+        }
+        if (has_next) {
+            float4 *da = (float4 *)A_s[buf ^ 1], *db = (float4 *)B_s[buf ^ 1];
+            da[tid] = pa0, da[tid + HL_THREADS] = pa1;
+            db[tid] = pb0r, db[tid + HL_THREADS] = pb1r;
+            if (third) da[tid + 2 * HL_THREADS] = pa2, db[tid + 2 * HL_THREADS] = pb2r;
+        }
+        if (c == HLL_NCH - 1) {
+            // ---- epilogue: this wave's 64 x 64 bounds, reduced by the duals, against tau ------------------------------------------
+            const int col0 = tile * HLL_BM + HL_BM * ch + lo, col1 = col0 + 32, row0 = HL_BM * rh + 4 * hi;
+            const double hb0 = hBf[col0], hb1 = hBf[col1];                               // (padded: +inf past the frame's end)
+            const double v0 = col0 < nB ? vf[col0] : 0.0, v1 = col1 < nB ? vf[col1] : 0.0;
+            unsigned long long mask = 0ull;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r0 = row0 + 8 * (e >> 2) + (e & 3), r1 = r0 + 32;
+                const double ha0 = hA_s[r0], ha1 = hA_s[r1], u0 = u_s[r0], u1 = u_s[r1];
+                const int s0 = skip_s[r0], s1 = skip_s[r1];
+                const double l00 = (ha0 + hb0) - (double)acc00[e], l01 = (ha0 + hb1) - (double)acc01[e];
+                const double l10 = (ha1 + hb0) - (double)acc10[e], l11 = (ha1 + hb1) - (double)acc11[e];
+                if ((l00 - v0) - u0 <= tau && col0 != s0) mask |= 1ull << e;
+                if ((l01 - v1) - u0 <= tau && col1 != s0) mask |= 1ull << (16 + e);
+                if ((l10 - v0) - u1 <= tau && col0 != s1) mask |= 1ull << (32 + e);
+                if ((l11 - v1) - u1 <= tau && col1 != s1) mask |= 1ull << (48 + e);
+                // four rows' values at a time: hoisting all 32 rows' LDS reads would cost the second wave per SIMD
+                if ((e & 3) == 3) {
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(mask != 0ull) != 0ull) {
+                const int mine = __popcll(mask);
+                int incl = mine;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int o = __shfl_up(incl, d, PM_WAVE);
+                    if (lane >= d) incl += o;
+                }
+                const int wave_total = __shfl(incl, 63, PM_WAVE);
+                unsigned int base_lo = 0, base_hi = 0;
+                if (lane == 0) {
+                    const unsigned long long b = atomicAdd(&cnt[f], (unsigned long long)wave_total);
+                    base_lo = (unsigned int)b, base_hi = (unsigned int)(b >> 32);
+                }
+                base_lo = __shfl(base_lo, 0, PM_WAVE), base_hi = __shfl(base_hi, 0, PM_WAVE);
+                unsigned long long slot = (((unsigned long long)base_hi << 32) | base_lo) + (unsigned long long)(incl - mine);
+                int2 *rc = (int2 *)out_rc + (size_t)f * cap;
+                double *ob = out_bound + (size_t)f * cap;
+                int grow0 = pb * HLL_BM + row0;
+                asm volatile("" : "+v"(grow0));          // (not a loop invariant: 32 row numbers would be kept in registers)
+#pragma unroll
+                for (int e = 0; e < 64; ++e) {
+                    if (!((mask >> e) & 1ull)) continue;
+                    const int q = e >> 4, ee = e & 15, rl = 8 * (ee >> 2) + (ee & 3) + 32 * (q >> 1);
+                    float dot = q == 0 ? acc00[ee] : q == 1 ? acc01[ee] : q == 2 ? acc10[ee] : acc11[ee];
+                    // (opaque to the compiler: the bound is formed again here, by the same operations, instead of 64 float64
+                    //  values of the test above staying live for this rare path — they would cost the second wave per SIMD)
+                    asm volatile("" : "+v"(dot));
+                    if (slot < (unsigned long long)cap) {
+                        rc[slot] = make_int2(grow0 + rl, (q & 1) ? col1 : col0);
+                        ob[slot] = (hA_s[row0 + rl] + ((q & 1) ? hb1 : hb0)) - (double)dot;
+                        asm volatile("" ::: "memory");
+                    }
+                    ++slot;
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.0f;
+        }
+        tile = ntile;
+        c = nc;
+        buf ^= 1;
+        __syncthreads();
+    }
+}
+
+struct HlListWorkspace {
+    size_t rA, rB, hA, hB, cnt, bytes;      // byte offsets
+};
+
+static HlListWorkspace hl_list_workspace(int nA, int nB, int F) {
+    const size_t PB = ((size_t)nA + HLL_BM - 1) / HLL_BM, CT = ((size_t)nB + HLL_BM - 1) / HLL_BM;
+    HlListWorkspace w;
+    size_t o = 0;
+    w.rA = o, o += align_up(PB * 2 * HL_TILE * sizeof(float), 256);
+    w.rB = o, o += align_up((size_t)F * CT * 2 * HL_TILE * sizeof(float), 256);
+    w.hA = o, o += align_up(PB * HLL_BM * sizeof(double), 256);
+    w.hB = o, o += align_up((size_t)F * CT * HLL_BM * sizeof(double), 256);
+    w.cnt = o, o += 256;
+    w.bytes = o;
+    return w;
+}
+
 }  // namespace pm
+
+extern "C" size_t pm_hellinger_list_workspace(int nA, int nB, int n_frames) {
+    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4) return 0;
+    return pm::hl_list_workspace(nA, nB, n_frames).bytes;
+}
+
+extern "C" int pm_hellinger_list(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames,
+                                 const double *u, const double *v, const int32_t *skip, double tau, int split, int32_t *out_rc,
+                                 double *out_bound, int cap, int32_t *count, int32_t *nonfinite1, void *ws, size_t ws_bytes,
+                                 void *stream) {
+    using namespace pm;
+    if (!scA || !scB || !u || !v || !out_rc || !out_bound || !count || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 ||
+        n_frames > 4 || cap <= 0 || split < 0 || tau != tau || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
+        return PM_ERR_INVALID_ARG;
+    const HlListWorkspace L = hl_list_workspace(nA, nB, n_frames);
+    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)ws;
+    float *rA = (float *)(base + L.rA), *rB = (float *)(base + L.rB);
+    double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
+    unsigned long long *cnt = (unsigned long long *)(base + L.cnt);
+    const long PB = ((long)nA + HLL_BM - 1) / HLL_BM, CT = ((long)nB + HLL_BM - 1) / HLL_BM;
+    // workgroups the column tiles of a (panel, frame) are divided over: the caller's, or enough for eight rounds of three per CU
+    // of a 256-CU device (a split costs nothing here — no partial lists, no merge — and short workgroups keep the last round full)
+    const long want = split > 0 ? split : (6144 + PB * n_frames - 1) / (PB * n_frames);
+    const int S = (int)std::max(1L, std::min({want, CT, (long)HL_SMAX}));
+    // a +inf bound (a padding or non-finite fixed row) fails the comparison against any finite tau: tau = +inf becomes the largest one
+    const double tau_f = std::min(tau, 1.7976931348623157e308);
+
+    hl_list_clear_kernel<<<1, 64, 0, s>>>(cnt, n_frames, nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((PB * HLL_BM + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, (int)(PB * HLL_BM), rA, hA,
+                                                                                     __builtin_nan(""), nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((CT * HLL_BM + 255) / 256), n_frames), 256, 0, s>>>(scB, frame_stride, nB, (int)(CT * HLL_BM),
+                                                                                            rB, hB, __builtin_inf(), nonfinite1);
+    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * n_frames));      // under 2^32 work-items per launch
+    for (long b0 = 0; b0 < PB; b0 += band) {
+        const long nb = std::min(band, PB - b0);
+        hl_list_kernel<<<dim3((unsigned int)(nb * S), n_frames), HL_THREADS, 0, s>>>(rA, rB, hA, hB, u, v, skip, tau_f, nA, nB, (int)CT,
+                                                                                    (int)b0, S, cap, out_rc, out_bound, cnt);
+    }
+    hl_list_finish_kernel<<<1, 64, 0, s>>>(cnt, n_frames, count);
+    return launch_status();
+}
 
 extern "C" size_t pm_hellinger_topk_workspace(int nA, int nB, int n_frames, int k) {
     if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 || k > pm::HL_KMAX) return 0;

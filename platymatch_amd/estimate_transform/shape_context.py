@@ -239,6 +239,33 @@ def unary_distance_candidates(sc_moving, unary_fixed, k=16):
     return nat.like_input(cols, sc_moving), nat.like_input(lower, sc_moving)
 
 
+def unary_distance_below(sc_moving, unary_fixed, threshold, row_offsets=None, col_offsets=None, exclude=None, cap=None):
+    """Every pair (moving nucleus i, fixed nucleus j) that CAN have get_unary_distance(a_i, b_j) - row_offsets[i] - col_offsets[j]
+    <= threshold, WITHOUT building a cost matrix: the Hellinger lower bound of unary_distance_candidates against a threshold
+    instead of a per-row top-k (K.hellinger_list).  sc_moving, unary_fixed: as for unary_distance_candidates; row_offsets [F, N] /
+    col_offsets [F, M] (an assignment solver's duals; [N] / [M] for a single frame; default zero); exclude [F, N]: per row one
+    column that is not wanted (its matched one), -1 for none.  NumPy or torch in, the same kind out.
+    -> per frame a tuple (rows int32, cols int32, lower float64) sorted by (row, column), lower = bound - K.hellinger_delta() <=
+    get_unary_distance(a_i, b_j); None for a frame with more than cap (default 64 * M) such pairs.
+    GUARANTEE (descriptor rows that sum to at most 1, as get_unary's do; finite rows and offsets): every pair that is NOT returned
+    and not excluded has get_unary_distance(a_i, b_j) - row_offsets[i] - col_offsets[j] > threshold."""
+    torch = nat.torch_mod()
+    a = nat.to_dev(sc_moving)
+    if _stacked(unary_fixed, len(unary_fixed)) or (nat.is_torch(unary_fixed) and unary_fixed.dim() == 2) or \
+            (isinstance(unary_fixed, np.ndarray) and unary_fixed.ndim == 2):
+        f = nat.to_dev(unary_fixed, dev=a.device)
+    else:
+        f = torch.stack([nat.to_dev(x, dev=a.device) for x in unary_fixed])
+    F, N, M = (1 if f.dim() == 2 else f.shape[0]), a.shape[0], f.shape[-2]
+    u = torch.zeros(F * N, dtype=torch.float64, device=a.device) if row_offsets is None else nat.to_dev(row_offsets, dev=a.device).reshape(-1)
+    v = torch.zeros(F * M, dtype=torch.float64, device=a.device) if col_offsets is None else nat.to_dev(col_offsets, dev=a.device).reshape(-1)
+    skip = None if exclude is None else nat.to_dev(exclude, dtype=torch.int32, dev=a.device).reshape(-1)
+    delta = K.hellinger_delta()
+    lists = K.hellinger_list(a.contiguous(), f.contiguous(), u, v, float(threshold) + delta, skip=skip, cap=cap)
+    return [None if x is None else (nat.like_input(x[0], sc_moving), nat.like_input(x[1], sc_moving), nat.like_input(x[2] - delta, sc_moving))
+            for x in lists]
+
+
 def _stacked(x, k):
     return nat.is_torch(x) and x.dim() == 3 and x.shape[0] == k and x.is_cuda
 

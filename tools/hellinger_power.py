@@ -4,11 +4,14 @@ with the product's own kernels — the two kill criteria of VERDICT.md "Next rou
   (i)  share of rows whose MATCHED column (the exact mode's assignment) lies inside the bound's top-k of the row;
   (ii) share of a row's columns whose bound lies below the row's 16th-smallest EXACT cost (what a per-row threshold cannot prune).
 Per pairing (U11, U12, U13, U14), for k = 16, 32, 64, plus the largest |L~ - L_float64| seen on sampled rows.
-Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel]
+Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel] [--list]
   --rows R       criteria on R evenly spaced rows instead of all (50 000 nuclei: the exact matrix of R rows at a time)
   --speed        also time hellinger_topk(k=16, four frames) against chi2_filter4(float32) + pm_lsap_row_select_f32(k=16) on the
                  four matrices: alternating, seven repetitions each after a warm-up, HIP events around work that ends in a synchronise
   --only-kernel  descriptors + one warm-up + one hellinger_topk call, nothing else (the subject of a rocprofv3 --kernel-trace run)
+  --list         the threshold listing (K.hellinger_list) and nothing else: its speed against hellinger_topk(k=16) at about 16
+                 entries per row (u = the row's 16th bound, v = 0, tau = 0; alternating, seven repetitions each), and the LIST SIZE
+                 of a matrix-free pricing round: entries listed per row under the final duals of the exact mode's device solve
 Prints to stdout; writes nothing."""
 import argparse
 import os
@@ -26,6 +29,7 @@ def main():
     ap.add_argument("--rows", type=int, default=0)
     ap.add_argument("--speed", action="store_true")
     ap.add_argument("--only-kernel", action="store_true")
+    ap.add_argument("--list", action="store_true")
     args = ap.parse_args()
     import torch
     import bench
@@ -52,6 +56,10 @@ def main():
         for _ in range(2):
             ms, _ = timed(lambda: K.hellinger_topk(a, sc_f, k=16))
         print("hellinger_topk(k=16, 4 frames): %.2f ms = %.1f TFLOP/s of 2*360*F*N*M" % (ms, 2 * 360 * 4 * n * n / ms / 1e9))
+        return
+
+    if args.list:
+        list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed)
         return
 
     if args.speed:
@@ -109,6 +117,47 @@ def main():
             line += "  k=%d %.2f %%" % (k, 100.0 * hit[match[rows] >= 0].mean())
         print(line)
     print("largest |bound - L_float64| on listed entries: %.3g (delta %.3g)" % (worst, delta))
+
+
+def list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed):
+    import types
+    flop = 2 * 360 * 4 * n * n
+    kth = K.hellinger_topk(a, sc_f, k=16)[1][:, :, 15].contiguous()
+    zero, info = torch.zeros((4, n), dtype=torch.float64, device=a.device), {}
+
+    def new():
+        return K.hellinger_list(a, sc_f, kth, zero, 0.0, info=info)
+
+    def old():
+        out = K.hellinger_topk(a, sc_f, k=16)
+        torch.cuda.synchronize()                  # (hellinger_list reads its counts back: both legs end in a synchronise)
+        return out
+    old(), new()
+    t_old, t_new = [], []
+    for _ in range(7):
+        t_old.append(timed(old)[0])
+        t_new.append(timed(new)[0])
+    print("list   entries per row at u = 16th bound, v = 0, tau = 0: %s" % ", ".join("%.2f" % (c / n) for c in info["count"]))
+    for name, t in (("hellinger_topk(k=16, 4 frames)", t_old), ("hellinger_list(4 frames), sort by (row, column) included", t_new)):
+        print("speed  %-58s median %8.2f ms  min %8.2f  max %8.2f  %6.1f TFLOP/s  (7 repetitions, alternating)"
+              % (name, np.median(t), min(t), max(t), flop / np.median(t) / 1e9))
+    sym = K.chi2_symmetric(sc_m, sc_f)
+    for t in range(4):
+        U = K.chi2_cost_pair(sc_m, sc_f, t, sym)[0]
+        sol = L.solve_core(L.DeviceMatrix(U), {})
+        del U
+        if sol is None:
+            print("pairing %d: the device solve gave no duals" % t)
+            continue
+        u, v, col4row = (np.asarray(x) for x in sol)
+        tau = L.FilteredMatrix._tau(types.SimpleNamespace(cost_delta=delta), u, v)
+        dev = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x), dtype=dt).to(a.device)
+        got = K.hellinger_list(a, sc_f[t].contiguous(), dev(u, torch.float64), dev(v, torch.float64), tau,
+                               skip=dev(col4row, torch.int32), cap=256 * n, info=info)[0]
+        per_row = torch.bincount(got[0].long(), minlength=n) if got is not None else None
+        print("pairing %d (U1%d): tau = %.3g; listed under the final duals: %d entries = %.2f per row (max %s); exceeds 64 * M: %s"
+              % (t, t + 1, tau, info["count"][0], info["count"][0] / n, "?" if per_row is None else int(per_row.max()),
+                 "YES" if info["count"][0] > 64 * n else "no"))
 
 
 if __name__ == "__main__":
