@@ -305,6 +305,26 @@ int pm_hellinger_list(const double *scA, int nA, const double *scB, int nB, size
                       int32_t *out_rc, double *out_bound, int cap, int32_t *count, int32_t *nonfinite1,
                       void *ws, size_t ws_bytes, void *stream);
 
+/* PRICED SELECTION from the same bound (hl_select_kernel), the matrix-free form of a solver's row_select(v, k): per frame f and
+ * moving row i the k columns of smallest  key = bound - v[f][j],  bound = (hA_i + hB_j) - (double)dot, both in float64 in that
+ * order — the bound has the bits pm_hellinger_topk and pm_hellinger_list report for the same entry.
+ *   scA, scB, frame_stride, n_frames: as above;  v [n_frames][nB] column prices (device), or NULL for none;  k 1..64;
+ *   split: workgroups the fixed rows are divided over per panel of 128 moving rows, 0 = automatic (the result does not depend
+ *   on it, bit for bit);
+ *   out_col, out_bound  [n_frames][nA][k], ascending by (key, column); out_bound holds the BOUND, not the key: the caller re-forms
+ *   the key as out_bound - v[out_col], the same subtraction with the same bits.  Tails and non-finite moving rows as for
+ *   pm_hellinger_topk (-1 / +inf, -1 / NaN).  A column whose price is NaN or +-inf is never listed, nor is a non-finite fixed
+ *   row; nonfinite1 reports the descriptor rows only.  With v == NULL or all prices +0.0, columns and bound bits are
+ *   pm_hellinger_topk's, for any split.
+ * CONTRACT, for descriptor rows with sum <= 1, finite prices with |v| <= 1e6 and delta = pm_hellinger_delta: every listed entry
+ * has C(i, col) - v[col] >= key - delta, and every column j that is NOT listed and has a finite price and fixed row has
+ * C(i, j) - v[j] >= key[k-1] - delta (the rounding of the one float64 subtraction lies in the slack pm_hellinger_list's contract
+ * already claims).  ws: pm_hellinger_select_workspace bytes, 16-byte aligned device memory. */
+size_t pm_hellinger_select_workspace(int nA, int nB, int n_frames, int k);
+int pm_hellinger_select(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames, const double *v,
+                        int k, int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1, void *ws, size_t ws_bytes,
+                        void *stream);
+
 /* Listed entries of one pairing's two EXACT matrices (the bits of pm_chi2_cost_pair_sym's): out_natural[e], out_rolled[e] =
  * entry (rows[e], cols[e]) of the natural-order matrix (U11, U12, U13, U14 for pairing 0..3) and of its rolled-order twin (U22,
  * U21, U24, U23).  rows / cols / outputs: device, n_entries each; an index out of range yields NaN in both outputs.  What turns

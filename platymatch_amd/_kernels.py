@@ -441,6 +441,44 @@ def hellinger_topk(sc_a, sc_b, k=16, split=0, info=None):
     return cols, bound
 
 
+def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None):
+    """Per row of sc_a [N, 360] the k columns of each fixed frame sc_b [F, M, 360] (or [M, 360]: F = 1) with the smallest
+    key = bound - v[f, j], the Hellinger lower bound reduced by column prices — an assignment solver's row_select(v, k) without a
+    matrix (pm_hellinger_select; csrc/pm_hellinger.hip: hl_select_kernel).  v: float64 GPU tensor [F, M] (or [M] for F = 1), or
+    None for no prices -> (cols int32 [F, N, k], bound float64 [F, N, k]), ascending by (key, column).  bound is the BOUND, with
+    the bits hellinger_topk / hellinger_list report for the entry: the key is bound - v[f, cols] (the same subtraction, the same
+    bits).  -1 / +inf where fewer than k columns can be listed, -1 / NaN for a non-finite row of sc_a; a column whose price is
+    NaN or infinite is never listed.  With v None or all +0.0 the result is hellinger_topk's, bit for bit.  Exact cost - v >=
+    key - hellinger_delta() for listed entries, >= key[..., -1] - hellinger_delta() for every other column with a finite price.
+    split: workgroups per panel of 128 rows (0 = automatic; same bits for any value).  info (dict): receives 'nonfinite' (of the
+    descriptors; synchronises)."""
+    torch = _t()
+    a = _desc(sc_a, "sc_a")
+    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
+            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
+        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
+    _here(sc_b, "sc_b")
+    k, split = int(k), int(split)
+    if not 1 <= k <= 64:
+        raise ValueError("k must be 1..64")
+    if split < 0:
+        raise ValueError("split must be >= 0 (0 = automatic)")
+    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
+    N, M = a.shape[0], sc_b.shape[-2]
+    if v is not None:
+        _here(_vec(v, F * M, "v"), "v")
+    lib = nat.load()
+    cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
+    bound = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
+    flag = torch.empty(1, dtype=torch.int32, device=a.device)
+    ws = nat.workspace(lib.pm_hellinger_select_workspace(N, M, F, k), a.device)
+    check(lib.pm_hellinger_select(ptr(a), N, ptr(sc_b), M, M * NBINS, F, ptr(v), k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws),
+                                  ws.numel(), nat.stream_ptr()))
+    if info is not None:
+        info["nonfinite"] = int(flag.item())
+    return cols, bound
+
+
 def _hellinger_list_raw(a, sc_b, u, v, skip, tau, split, rc, bound, cap, count, flag):
     """One pm_hellinger_list call on prepared tensors (the outputs may be longer than cap: the tests' guard tails)."""
     F = 1 if sc_b.dim() == 2 else sc_b.shape[0]

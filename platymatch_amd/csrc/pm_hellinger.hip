@@ -598,6 +598,361 @@ static HlListWorkspace hl_list_workspace(int nA, int nB, int F) {
     return w;
 }
 
+// ---- priced selection: per row the k entries of smallest bound reduced by the column prices ---------------------------------
+// hl_select_kernel answers the solver's row_select(v, k): per (frame, moving row) the k columns of smallest
+//     key = L~ - v[f][j]   (float64, in that order),   L~ = (hA_i + hB_j) - (double)dot — the bits of the two kernels above,
+// ascending by (key, column); what is reported beside the column is the BOUND L~ (the caller re-forms the key by the same
+// subtraction).  A column whose price is NaN or +-inf is treated as a non-finite fixed row: its hB becomes +inf, it is never listed.
+// With v == NULL (or all prices +0.0) key = L~ bit for bit, and the lists are hl_topk_kernel's.
+// Geometry: hl_list_kernel's streamed one (a panel of 128 moving rows against 128-column tiles, both operands through two
+// 20-bin LDS stages, four independent MFMA chains per wave, bins 0..359 in order) — nothing of the panel is resident but its
+// per-row STATE: hA, tau (the row's current k-th key; DBL_MAX until k entries are known, so a +inf key never passes), a count and
+// a buffer of CAP slots of (dot float32, column int32).  Epilogue: 64 keys per lane per tile in float64 against tau into a 64-bit
+// mask (as the listing kernel forms its mask); the set bits are appended through an LDS atomic on the row's count.  A full buffer
+// is cut to its k smallest by (key, column) by one wave (ranks by counting) and tau lowered; lanes that found no slot retry
+// after the cut — the ovf protocol of hl_topk_kernel, one more barrier per tile of 18 stages.  An entry is only ever dropped
+// against a tau that k better entries of the row have set, so the final buffer holds the row's exact top-k whatever the order
+// of the appends, and the final ranking by (key, column) makes the list deterministic.
+// CAP is a template parameter: 32 for k <= 16 (LDS 40 960 of stages + 32 768 of buffers + 3 592 = 77 320 B, 196 registers: two
+// workgroups per CU, two waves per SIMD), 80 for k <= 64 (128 008 B, one workgroup per CU); both leave CAP - k >= 16 free slots
+// after a cut.  No scratch in either.
+// Measured (profiles/hellinger_select_20k.txt): 20 000 x 20 000 x 4 frames, the whole call: 14.9 ms at k = 16, 13.6 ms at k = 8,
+// with and without prices, against hl_topk_kernel's call at 22.3 ms.
+// Column tiles are split over S workgroups per (panel, frame); each writes its sorted partial list of (column, bound) and
+// hl_select_merge_kernel re-forms the keys and merges by (key, column): disjoint column sets, exact partial lists, the same
+// subtraction — the result does not depend on S.
+constexpr int HLS_SPLIT_ROWS = 512 * HLL_BM;      // rows x splits never exceeds this (workspace of the partial lists)
+constexpr double HLS_TAU0 = 1.7976931348623157e308;
+
+template <int NQ>
+struct HlsEntries {      // a lane's (at most NQ) entries of the row being ranked
+    float dot[NQ];
+    int col[NQ];
+    double b[NQ], key[NQ];
+    int rank[NQ];
+    bool valid[NQ];
+};
+
+// hl_rank_row for keys: ranks by (key, column) of the n <= CAP buffered entries of one row, by one wave.  sv: CAP doubles of this
+// wave's scratch; vf: the frame's prices or NULL (buffered columns have finite prices).
+template <int CAP>
+__device__ __forceinline__ void hls_rank_row(const float *cd, const int32_t *cc, int n, double ha, const double *__restrict__ hBf,
+                                             const double *__restrict__ vf, double *sv, int lane, HlsEntries<(CAP + 63) / 64> &e) {
+    constexpr int NQ = (CAP + 63) / 64;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int idx = lane + 64 * q;
+        e.valid[q] = idx < n;
+        e.dot[q] = e.valid[q] ? cd[idx] : 0.0f;
+        e.col[q] = e.valid[q] ? cc[idx] : INT_MAX;
+        e.b[q] = e.valid[q] ? (ha + hBf[e.col[q]]) - (double)e.dot[q] : __builtin_inf();
+        e.key[q] = e.valid[q] ? e.b[q] - (vf ? vf[e.col[q]] : 0.0) : __builtin_inf();
+        if (idx < CAP) sv[idx] = e.key[q];
+        e.rank[q] = 0;
+    }
+    hl_wave_sync();
+    for (int j = 0; j < n; ++j) {
+        const double vj = sv[j];
+        const int cj = cc[j];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) e.rank[q] += (vj < e.key[q] || (vj == e.key[q] && cj < e.col[q])) ? 1 : 0;
+    }
+    hl_wave_sync();
+}
+
+// out_col / out_val: the final arrays [F][nA][k] when S == 1, the partial lists [F][nA][S][k] otherwise.
+template <int CAP>
+__global__ __launch_bounds__(HL_THREADS, 2) void hl_select_kernel(const float *__restrict__ rAt, const float *__restrict__ rBt,
+                                                               const double *__restrict__ hA, const double *__restrict__ hB,
+                                                               const double *__restrict__ v, int nA, int nB, int CT, int pb0, int S,
+                                                               int k, int32_t *__restrict__ out_col, double *__restrict__ out_val) {
+    __shared__ __attribute__((aligned(16))) float A_s[2][HLL_STAGE];
+    __shared__ __attribute__((aligned(16))) float B_s[2][HLL_STAGE];
+    __shared__ float cd_s[HLL_BM][CAP];
+    __shared__ int32_t cc_s[HLL_BM][CAP];
+    __shared__ double sv_s[HL_THREADS / 64][CAP];
+    __shared__ double hA_s[HLL_BM], tau_s[HLL_BM];
+    __shared__ int cnt_s[HLL_BM];
+    __shared__ int ovf_s;
+
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, rh = w & 1, ch = w >> 1;
+    const int pb = pb0 + (int)(blockIdx.x / (unsigned int)S), sp = (int)(blockIdx.x % (unsigned int)S), f = blockIdx.y;
+    const int t0 = (int)((long)sp * CT / S), t1 = (int)((long)(sp + 1) * CT / S);      // S <= CT: at least one tile
+    const double inf = __builtin_inf();
+    const double *hBf = hB + (size_t)f * CT * HLL_BM;
+    const double *vf = v ? v + (size_t)f * nB : nullptr;
+    const float4 *at4 = (const float4 *)(rAt + (size_t)pb * 2 * HL_TILE);
+    const float4 *bt4 = (const float4 *)(rBt + (size_t)f * CT * 2 * HL_TILE);
+
+    if (tid < HLL_BM) {
+        hA_s[tid] = hA[(size_t)pb * HLL_BM + tid];                                      // (padded: NaN past the cloud's end)
+        tau_s[tid] = HLS_TAU0;
+        cnt_s[tid] = 0;
+    }
+    if (tid == 0) ovf_s = 0;
+
+    // the stage copies and operand offsets of hl_list_kernel
+    int so[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int j = tid + HL_THREADS * q;
+        so[q] = (j / (HLL_HALF / 4)) * (HL_TILE / 4) + j % (HLL_HALF / 4);
+    }
+    const bool third = tid < HL_THREADS / 2;
+    const int hi = lane >> 5, lo = lane & 31;
+    const int off0 = hi * HL_BM + ((lo + 32 * hi) & 63), off1 = hi * HL_BM + ((32 + lo + 32 * hi) & 63);
+
+    float4 pa0, pa1, pa2 = make_float4(0.f, 0.f, 0.f, 0.f), pb0r, pb1r, pb2r = make_float4(0.f, 0.f, 0.f, 0.f);
+    {
+        const float4 *sb = bt4 + (size_t)t0 * (2 * HL_TILE / 4);
+        pa0 = at4[so[0]], pa1 = at4[so[1]];
+        pb0r = sb[so[0]], pb1r = sb[so[1]];
+        if (third) pa2 = at4[so[2]], pb2r = sb[so[2]];
+        float4 *da = (float4 *)A_s[0], *db = (float4 *)B_s[0];
+        da[tid] = pa0, da[tid + HL_THREADS] = pa1;
+        db[tid] = pb0r, db[tid + HL_THREADS] = pb1r;
+        if (third) da[tid + 2 * HL_THREADS] = pa2, db[tid + 2 * HL_THREADS] = pb2r;
+    }
+    __syncthreads();
+
+    hl_f16 acc00, acc01, acc10, acc11;              // (row half, column half) of the wave's 64 x 64
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.0f;
+    int tile = t0, c = 0, buf = 0;
+    const long total = (long)(t1 - t0) * HLL_NCH;
+    for (long st = 0; st < total; ++st) {
+        const bool has_next = st + 1 < total;
+        const int nc = (c + 1 == HLL_NCH) ? 0 : c + 1, ntile = (c + 1 == HLL_NCH) ? tile + 1 : tile;
+        if (has_next) {
+            const float4 *sa = at4 + nc * (HLL_HALF / 4);
+            const float4 *sb = bt4 + (size_t)ntile * (2 * HL_TILE / 4) + nc * (HLL_HALF / 4);
+            pa0 = sa[so[0]], pa1 = sa[so[1]];
+            pb0r = sb[so[0]], pb1r = sb[so[1]];
+            if (third) pa2 = sa[so[2]], pb2r = sb[so[2]];
+        }
+        const float *Ab = A_s[buf] + rh * HLL_HALF, *Bb = B_s[buf] + ch * HLL_HALF;
+#pragma unroll
+        for (int m = 0; m < HLL_KC / 2; ++m) {
+            const float a0 = Ab[m * 128 + off0], a1 = Ab[m * 128 + off1], b0 = Bb[m * 128 + off0], b1 = Bb[m * 128 + off1];
+            acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc00, 0, 0, 0);
+            acc01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc01, 0, 0, 0);
+            acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc10, 0, 0, 0);
+            acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc11, 0, 0, 0);
+        }
+        if (has_next) {
+            float4 *da = (float4 *)A_s[buf ^ 1], *db = (float4 *)B_s[buf ^ 1];
+            da[tid] = pa0, da[tid + HL_THREADS] = pa1;
+            db[tid] = pb0r, db[tid + HL_THREADS] = pb1r;
+            if (third) da[tid + 2 * HL_THREADS] = pa2, db[tid + 2 * HL_THREADS] = pb2r;
+        }
+        if (c == HLL_NCH - 1) {
+            // ---- epilogue: this wave's 64 x 64 keys against the rows' thresholds -----------------------------------------------
+            const int col0 = tile * HLL_BM + HL_BM * ch + lo, col1 = col0 + 32, row0 = HL_BM * rh + 4 * hi;
+            double hb0 = hBf[col0], hb1 = hBf[col1];                                     // (padded: +inf past the frame's end)
+            double v0 = (vf && col0 < nB) ? vf[col0] : 0.0, v1 = (vf && col1 < nB) ? vf[col1] : 0.0;
+            if (!(v0 - v0 == 0.0)) hb0 = inf, v0 = 0.0;                                  // a NaN or infinite price: never listed
+            if (!(v1 - v1 == 0.0)) hb1 = inf, v1 = 0.0;
+            unsigned long long pending = 0ull;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int r0 = row0 + 8 * (e >> 2) + (e & 3), r1 = r0 + 32;
+                const double ha0 = hA_s[r0], ha1 = hA_s[r1], tau0 = tau_s[r0], tau1 = tau_s[r1];
+                const double l00 = (ha0 + hb0) - (double)acc00[e], l01 = (ha0 + hb1) - (double)acc01[e];
+                const double l10 = (ha1 + hb0) - (double)acc10[e], l11 = (ha1 + hb1) - (double)acc11[e];
+                if (l00 - v0 <= tau0) pending |= 1ull << e;
+                if (l01 - v1 <= tau0) pending |= 1ull << (16 + e);
+                if (l10 - v0 <= tau1) pending |= 1ull << (32 + e);
+                if (l11 - v1 <= tau1) pending |= 1ull << (48 + e);
+                // four rows' values at a time, as in hl_list_kernel: all 32 rows' LDS reads at once would cost the second wave
+                if ((e & 3) == 3) {
+                    asm volatile("" ::: "memory");
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            for (;;) {
+                if (pending != 0ull) {
+#pragma unroll
+                    for (int e = 0; e < 64; ++e) {
+                        if (!((pending >> e) & 1ull)) continue;
+                        const int q = e >> 4, ee = e & 15, row = row0 + 8 * (ee >> 2) + (ee & 3) + 32 * (q >> 1);
+                        float dot = q == 0 ? acc00[ee] : q == 1 ? acc01[ee] : q == 2 ? acc10[ee] : acc11[ee];
+                        // (opaque to the compiler: the key is formed again here, by the same operations, instead of 64 float64
+                        //  values of the test above staying live for this rare path)
+                        asm volatile("" : "+v"(dot));
+                        const double key = ((hA_s[row] + ((q & 1) ? hb1 : hb0)) - (double)dot) - ((q & 1) ? v1 : v0);
+                        bool done = true;
+                        if (key <= tau_s[row]) {             // (again: a cut may have lowered tau since the mask was formed)
+                            const int slot = atomicAdd(&cnt_s[row], 1);
+                            if (slot < CAP) {
+                                cd_s[row][slot] = dot;
+                                cc_s[row][slot] = (q & 1) ? col1 : col0;
+                            } else {
+                                done = false;
+                                ovf_s = 1;
+                            }
+                        }
+                        if (done) pending &= ~(1ull << e);
+                        asm volatile("" ::: "memory");
+                    }
+                }
+                __syncthreads();
+                if (ovf_s == 0) break;           // (uniform: read between two barriers)
+                __syncthreads();
+                if (tid == 0) ovf_s = 0;
+                for (int r = w; r < HLL_BM; r += HL_THREADS / 64) {
+                    if (__builtin_amdgcn_readfirstlane(cnt_s[r]) < CAP) continue;
+                    HlsEntries<(CAP + 63) / 64> en;
+                    hls_rank_row<CAP>(cd_s[r], cc_s[r], CAP, hA_s[r], hBf, vf, sv_s[w], lane, en);
+#pragma unroll
+                    for (int q = 0; q < (CAP + 63) / 64; ++q)
+                        if (en.valid[q] && en.rank[q] < k) {
+                            cd_s[r][en.rank[q]] = en.dot[q];
+                            cc_s[r][en.rank[q]] = en.col[q];
+                            if (en.rank[q] == k - 1) tau_s[r] = en.key[q];
+                        }
+                    if (lane == 0) cnt_s[r] = k;
+                    hl_wave_sync();
+                }
+                __syncthreads();
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.0f;
+        }
+        tile = ntile;
+        c = nc;
+        buf ^= 1;
+        __syncthreads();
+    }
+
+    // ---- the rows' lists, ascending by (key, column); the bound is what is written ---------------------------------------------
+    for (int r = w; r < HLL_BM; r += HL_THREADS / 64) {
+        const long row = (long)pb * HLL_BM + r;
+        if (row >= nA) break;
+        const size_t base = (((size_t)f * nA + row) * S + sp) * k;
+        const double ha = hA_s[r];
+        if (ha != ha) {          // a non-finite moving row
+            for (int t = lane; t < k; t += 64) {
+                out_col[base + t] = -1;
+                out_val[base + t] = ha;
+            }
+            continue;
+        }
+        const int n = min(__builtin_amdgcn_readfirstlane(cnt_s[r]), CAP);
+        HlsEntries<(CAP + 63) / 64> en;
+        hls_rank_row<CAP>(cd_s[r], cc_s[r], n, ha, hBf, vf, sv_s[w], lane, en);
+#pragma unroll
+        for (int q = 0; q < (CAP + 63) / 64; ++q)
+            if (en.valid[q] && en.rank[q] < k) {
+                out_col[base + en.rank[q]] = en.col[q];
+                out_val[base + en.rank[q]] = en.b[q];
+            }
+        for (int t = min(n, k) + lane; t < k; t += 64) {
+            out_col[base + t] = -1;
+            out_val[base + t] = inf;
+        }
+    }
+}
+
+// hl_merge_kernel for keys: the S sorted partial lists (column, bound) of one (frame, row) -> its k smallest by (key, column),
+// key = bound - v[column] re-formed by the subtraction hl_select_kernel ranked with.  One wave per row; the lane that holds the
+// winning head writes it.
+__global__ __launch_bounds__(256) void hl_select_merge_kernel(const int32_t *__restrict__ pcol, const double *__restrict__ pval,
+                                                              const double *__restrict__ hA, const double *__restrict__ v, int nA,
+                                                              int nB, int S, int k, int32_t *__restrict__ out_col,
+                                                              double *__restrict__ out_val) {
+    const int lane = threadIdx.x & 63, f = blockIdx.y;
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= nA) return;
+    const size_t base = ((size_t)f * nA + row) * S * k, obase = ((size_t)f * nA + row) * k;
+    const double *vf = v ? v + (size_t)f * nB : nullptr;
+    const double inf = __builtin_inf(), ha = hA[row];
+    if (ha != ha) {
+        for (int t = lane; t < k; t += 64) {
+            out_col[obase + t] = -1;
+            out_val[obase + t] = ha;
+        }
+        return;
+    }
+    int pos[4], hc[4];
+    double hb[4], hk[4];
+    auto load = [&](int q) {      // the head of list lane + 64 q at pos[q]: INT_MAX / +inf past its end
+        const int l = lane + 64 * q;
+        hc[q] = (l < S && pos[q] < k) ? pcol[base + (size_t)l * k + pos[q]] : -1;
+        hb[q] = hc[q] >= 0 ? pval[base + (size_t)l * k + pos[q]] : inf;
+        hk[q] = hc[q] >= 0 ? hb[q] - (vf ? vf[hc[q]] : 0.0) : inf;
+        if (hc[q] < 0) hc[q] = INT_MAX;
+    };
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        pos[q] = 0;
+        load(q);
+    }
+    for (int t = 0; t < k; ++t) {
+        double bk = hk[0];
+        int bc = hc[0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q)
+            if (hk[q] < bk || (hk[q] == bk && hc[q] < bc)) {
+                bk = hk[q];
+                bc = hc[q];
+            }
+        double mk = bk;
+        int mc = bc;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double ok = __shfl_xor(mk, off, PM_WAVE);
+            const int oc = __shfl_xor(mc, off, PM_WAVE);
+            if (ok < mk || (ok == mk && oc < mc)) {
+                mk = ok;
+                mc = oc;
+            }
+        }
+        if (mc == INT_MAX) {
+            if (lane == 0) {
+                out_col[obase + t] = -1;
+                out_val[obase + t] = inf;
+            }
+            continue;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (hc[q] == mc) {          // (columns are distinct: exactly one head of one lane)
+                out_col[obase + t] = mc;
+                out_val[obase + t] = hb[q];
+                ++pos[q];
+                load(q);
+            }
+    }
+}
+
+struct HlSelectWorkspace {
+    size_t rA, rB, hA, hB, pcol, pval, bytes;      // byte offsets
+};
+
+static HlSelectWorkspace hl_select_workspace(int nA, int nB, int F, int k) {
+    const size_t PB = ((size_t)nA + HLL_BM - 1) / HLL_BM, CT = ((size_t)nB + HLL_BM - 1) / HLL_BM;
+    const size_t P = std::min(PB * HLL_BM * HL_SMAX, (size_t)HLS_SPLIT_ROWS);      // rows x splits of the partial lists, per frame
+    HlSelectWorkspace w;
+    size_t o = 0;
+    w.rA = o, o += align_up(PB * 2 * HL_TILE * sizeof(float), 256);
+    w.rB = o, o += align_up((size_t)F * CT * 2 * HL_TILE * sizeof(float), 256);
+    w.hA = o, o += align_up(PB * HLL_BM * sizeof(double), 256);
+    w.hB = o, o += align_up((size_t)F * CT * HLL_BM * sizeof(double), 256);
+    w.pcol = o, o += align_up((size_t)F * P * k * sizeof(int32_t), 256);
+    w.pval = o, o += align_up((size_t)F * P * k * sizeof(double), 256);
+    w.bytes = o;
+    return w;
+}
+
+// hl_splits for panels: the caller's, or enough workgroups for four rounds of two per CU of a 256-CU device (a split repeats the
+// first tiles' cuts and adds a merge, but a last round that is a quarter full costs more); never more than there are tiles,
+// than HL_SMAX, or than the partial lists' workspace holds
+static int hl_select_splits(int split, long PB, long CT, int F) {
+    const long cap = std::min({CT, (long)HL_SMAX, std::max(1L, (long)(HLS_SPLIT_ROWS / HLL_BM) / PB)});
+    const long want = split > 0 ? split : (2048 + PB * F - 1) / (PB * F);
+    return (int)std::max(1L, std::min(want, cap));
+}
+
 }  // namespace pm
 
 extern "C" size_t pm_hellinger_list_workspace(int nA, int nB, int n_frames) {
@@ -640,6 +995,50 @@ extern "C" int pm_hellinger_list(const double *scA, int nA, const double *scB, i
                                                                                     (int)b0, S, cap, out_rc, out_bound, cnt);
     }
     hl_list_finish_kernel<<<1, 64, 0, s>>>(cnt, n_frames, count);
+    return launch_status();
+}
+
+extern "C" size_t pm_hellinger_select_workspace(int nA, int nB, int n_frames, int k) {
+    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 || k > pm::HL_KMAX) return 0;
+    return pm::hl_select_workspace(nA, nB, n_frames, k).bytes;
+}
+
+extern "C" int pm_hellinger_select(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames,
+                                   const double *v, int k, int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1,
+                                   void *ws, size_t ws_bytes, void *stream) {
+    using namespace pm;
+    if (!scA || !scB || !out_col || !out_bound || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 ||
+        k > HL_KMAX || split < 0 || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
+        return PM_ERR_INVALID_ARG;
+    const HlSelectWorkspace L = hl_select_workspace(nA, nB, n_frames, k);
+    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char *base = (char *)ws;
+    float *rA = (float *)(base + L.rA), *rB = (float *)(base + L.rB);
+    double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
+    int32_t *pcol = (int32_t *)(base + L.pcol);
+    double *pval = (double *)(base + L.pval);
+    const long PB = ((long)nA + HLL_BM - 1) / HLL_BM, CT = ((long)nB + HLL_BM - 1) / HLL_BM;
+    const int S = hl_select_splits(split, PB, CT, n_frames);
+    int32_t *oc = S == 1 ? out_col : pcol;
+    double *ov = S == 1 ? out_bound : pval;
+
+    hl_clear_flag_kernel<<<1, 1, 0, s>>>(nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((PB * HLL_BM + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, (int)(PB * HLL_BM), rA, hA,
+                                                                                     __builtin_nan(""), nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((CT * HLL_BM + 255) / 256), n_frames), 256, 0, s>>>(scB, frame_stride, nB, (int)(CT * HLL_BM),
+                                                                                            rB, hB, __builtin_inf(), nonfinite1);
+    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * n_frames));      // under 2^32 work-items per launch
+    for (long b0 = 0; b0 < PB; b0 += band) {
+        const dim3 grid((unsigned int)(std::min(band, PB - b0) * S), n_frames);
+        if (k <= 16)
+            hl_select_kernel<32><<<grid, HL_THREADS, 0, s>>>(rA, rB, hA, hB, v, nA, nB, (int)CT, (int)b0, S, k, oc, ov);
+        else
+            hl_select_kernel<HL_CAP><<<grid, HL_THREADS, 0, s>>>(rA, rB, hA, hB, v, nA, nB, (int)CT, (int)b0, S, k, oc, ov);
+    }
+    if (S > 1)
+        hl_select_merge_kernel<<<dim3((unsigned int)((nA + 3) / 4), n_frames), 256, 0, s>>>(pcol, pval, hA, v, nA, nB, S, k, out_col,
+                                                                                           out_bound);
     return launch_status();
 }
 

@@ -211,7 +211,7 @@ def unary_distance_matrices(unary_moving, unary_fixed, out=None):
     return U if (nat.is_torch(unary_moving[0]) or out is not None) else U.cpu().numpy()
 
 
-def unary_distance_candidates(sc_moving, unary_fixed, k=16):
+def unary_distance_candidates(sc_moving, unary_fixed, k=16, col_offsets=None):
     """Per moving nucleus the k fixed nuclei that can be cheapest, WITHOUT building a cost matrix: the Hellinger lower bound
     0.5 (sum a + sum b) - sum sqrt(a) sqrt(b) <= get_unary_distance(a, b), as a float32 GEMM on the matrix cores fused with a
     per-row top-k (K.hellinger_topk).  sc_moving: ONE of get_unary(..., 'moving')'s arrays [N, 360]; unary_fixed: the tuple (or
@@ -226,7 +226,13 @@ def unary_distance_candidates(sc_moving, unary_fixed, k=16):
     U22 / U21 / U24 / U23 consist of the same terms as U11 / U12 / U13 / U14, so the first array's lists serve both.  The lists for
     MORE moving than fixed nuclei (the assignment then takes the fixed nuclei as its rows) come from calling this with the
     roles swapped — the bound is symmetric in its two arguments frame for frame, and under the permutation relation every
-    pairing's bin map is an involution: unary_distance_candidates(fixed frame 1, the moving frames) lists rows of U^T."""
+    pairing's bin map is an involution: unary_distance_candidates(fixed frame 1, the moving frames) lists rows of U^T.
+    col_offsets [F, M] ([M] for a single frame; an assignment solver's column prices): the lists are then the k columns of
+    smallest REDUCED value lower - col_offsets, ascending by (reduced value, column), as a solver's row_select(v, k) asks
+    (K.hellinger_select).  lower is still returned unreduced: form the reduced value of an entry as
+    lower[f, i, r] - col_offsets[f, cols[f, i, r]].  Then get_unary_distance(a_i, b_j) - col_offsets[f, j] is at least that value
+    for a listed entry and at least the row's last reduced value for every column that is not listed (finite offsets up to 1e6
+    in size); a column whose offset is NaN or infinite is never listed."""
     torch = nat.torch_mod()
     a = nat.to_dev(sc_moving)
     if _stacked(unary_fixed, len(unary_fixed)) or (nat.is_torch(unary_fixed) and unary_fixed.dim() == 2) or \
@@ -234,7 +240,11 @@ def unary_distance_candidates(sc_moving, unary_fixed, k=16):
         f = nat.to_dev(unary_fixed, dev=a.device)
     else:
         f = torch.stack([nat.to_dev(x, dev=a.device) for x in unary_fixed])
-    cols, bound = K.hellinger_topk(a.contiguous(), f.contiguous(), k=k)
+    if col_offsets is None:
+        cols, bound = K.hellinger_topk(a.contiguous(), f.contiguous(), k=k)
+    else:
+        v = nat.to_dev(col_offsets, dev=a.device).reshape(-1)
+        cols, bound = K.hellinger_select(a.contiguous(), f.contiguous(), v=v, k=k)
     lower = bound - K.hellinger_delta()
     return nat.like_input(cols, sc_moving), nat.like_input(lower, sc_moving)
 

@@ -4,7 +4,7 @@ with the product's own kernels — the two kill criteria of VERDICT.md "Next rou
   (i)  share of rows whose MATCHED column (the exact mode's assignment) lies inside the bound's top-k of the row;
   (ii) share of a row's columns whose bound lies below the row's 16th-smallest EXACT cost (what a per-row threshold cannot prune).
 Per pairing (U11, U12, U13, U14), for k = 16, 32, 64, plus the largest |L~ - L_float64| seen on sampled rows.
-Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel] [--list]
+Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel] [--list] [--select]
   --rows R       criteria on R evenly spaced rows instead of all (50 000 nuclei: the exact matrix of R rows at a time)
   --speed        also time hellinger_topk(k=16, four frames) against chi2_filter4(float32) + pm_lsap_row_select_f32(k=16) on the
                  four matrices: alternating, seven repetitions each after a warm-up, HIP events around work that ends in a synchronise
@@ -12,6 +12,8 @@ Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-ke
   --list         the threshold listing (K.hellinger_list) and nothing else: its speed against hellinger_topk(k=16) at about 16
                  entries per row (u = the row's 16th bound, v = 0, tau = 0; alternating, seven repetitions each), and the LIST SIZE
                  of a matrix-free pricing round: entries listed per row under the final duals of the exact mode's device solve
+  --select       the priced selection (K.hellinger_select) and nothing else: its speed against hellinger_topk(k=16) at k = 16 and
+                 k = 8, with v = 0 and with v = the bound's column minima (alternating, seven repetitions each after a warm-up)
 Prints to stdout; writes nothing."""
 import argparse
 import os
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--speed", action="store_true")
     ap.add_argument("--only-kernel", action="store_true")
     ap.add_argument("--list", action="store_true")
+    ap.add_argument("--select", action="store_true")
     args = ap.parse_args()
     import torch
     import bench
@@ -60,6 +63,10 @@ def main():
 
     if args.list:
         list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed)
+        return
+
+    if args.select:
+        select_leg(torch, K, a, sc_f, n, timed)
         return
 
     if args.speed:
@@ -158,6 +165,36 @@ def list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed):
         print("pairing %d (U1%d): tau = %.3g; listed under the final duals: %d entries = %.2f per row (max %s); exceeds 64 * M: %s"
               % (t, t + 1, tau, info["count"][0], info["count"][0] / n, "?" if per_row is None else int(per_row.max()),
                  "YES" if info["count"][0] > 64 * n else "no"))
+
+
+def select_leg(torch, K, a, sc_f, n, timed):
+    flop = 2 * 360 * 4 * n * n
+    zero = torch.zeros((4, n), dtype=torch.float64, device=a.device)
+    # the bound's column minima: the top-1 of the transposed problem, frame by frame (the bound is symmetric in its arguments)
+    vmin = torch.stack([K.hellinger_topk(sc_f[f].contiguous(), a, k=1)[1][0, :, 0] for f in range(4)]).contiguous()
+
+    def leg(fn):
+        def run():
+            out = fn()
+            torch.cuda.synchronize()
+            return out
+        return run
+    legs = [("hellinger_topk(k=16, 4 frames)", leg(lambda: K.hellinger_topk(a, sc_f, k=16)))]
+    for k in (16, 8):
+        for name, v in (("v = 0", zero), ("v = column minima", vmin)):
+            legs.append(("hellinger_select(k=%d, %s)" % (k, name), leg(lambda k=k, v=v: K.hellinger_select(a, sc_f, v=v, k=k))))
+    outs = [run() for _, run in legs]                     # warm-up; and the unpriced lists are the top-k kernel's, bit for bit
+    same = torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1].view(torch.int64), outs[1][1].view(torch.int64))
+    print("select (k=16, v = 0) against hellinger_topk(k=16): columns and bound bits %s" % ("identical" if same else "DIFFER"))
+    moved = (outs[2][0] != outs[0][0]).any(dim=2).float().mean().item()
+    print("select rows whose list changes under v = column minima: %.1f %%" % (100.0 * moved))
+    times = [[] for _ in legs]
+    for _ in range(7):
+        for t, (_, run) in zip(times, legs):
+            t.append(timed(run)[0])
+    for (name, _), t in zip(legs, times):
+        print("speed  %-46s median %8.2f ms  min %8.2f  max %8.2f  %6.1f TFLOP/s  (7 repetitions, alternating)"
+              % (name, np.median(t), min(t), max(t), flop / np.median(t) / 1e9))
 
 
 if __name__ == "__main__":
