@@ -325,6 +325,36 @@ int pm_hellinger_select(const double *scA, int nA, const double *scB, int nB, si
                         int k, int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1, void *ws, size_t ws_bytes,
                         void *stream);
 
+/* EXACT RESCORING of such lists (csrc/pm_chi2_select.hip: chi2_select_kernel), the step from the bound to exact costs: every
+ * candidate of every list is evaluated with the exact build's bits, each row is ordered by exact reduced cost, and the call
+ * reports how many leading entries are PROVEN to be the row's true smallest.  One launch, no N x M matrix, no workspace.
+ *   scA, scB, frame_stride, n_frames, v: as for pm_hellinger_select (scA, scB 16-byte aligned, frame_stride even: rows are read
+ *   as 16-byte pieces);  cand_col, cand_bound [n_frames][nA][kc]: the lists as pm_hellinger_select(k = kc) writes them, the BOUND
+ *   (not the key) beside each column;  1 <= k <= kc <= 64;  delta >= 0: the error bound of the lists' bound (pm_hellinger_delta).
+ * Per UNIT (frame f, moving row i):
+ *   - cost: for a candidate column c in [0, nB), C = 0.5 sum_{bin 0..359} (a-b)^2/(a+b) by chi2_kernel's operations, one rounding
+ *     each — a zero of b replaced by 1e-300, df = a - b, df*df, a + b, the correctly rounded quotient, bins added in index order,
+ *     the sum halved at the end: out_cost carries pm_chi2_cost's bits for the entry;
+ *   - twin (out_twin, may be NULL): the same 360 terms summed in rolled order (within each shell of 12: p = 6..11, 0..5), halved:
+ *     where the fixed frames are the phi permutations of frame 1, the bits of pm_chi2_entries_sym's out_rolled for pairing f;
+ *   - order: key = C - v[f][c] (one float64 subtraction; C itself when v == NULL); the k best candidates by (key, column)
+ *     ascending go to out_col / out_cost / out_twin [f][i][0..k), the cost UNREDUCED.  A candidate -1 is absent; absent output
+ *     slots hold column -1, cost +inf, twin +inf.  A candidate outside [-1, nB) is treated as absent and sets bit 1 (value 2) of
+ *     status1[0].  A unit whose candidates are all -1 with a NaN bound (pm_hellinger_select's non-finite moving row) gets
+ *     -1 / NaN / NaN, proven 0, and sets bit 0 of status1[0].  Columns of a list are expected to be distinct;
+ *   - proof: T = +inf if cand_col[kc-1] == -1 (the list then holds every listable column), else
+ *     T = (cand_bound[kc-1] - v[f][cand_col[kc-1]]) - delta in float64, in that order (NaN — nothing proven — if that last
+ *     candidate is out of range).  out_proven[f][i] = the number of leading output entries, at most k, with key < T, strictly.
+ * GUARANTEE, under pm_hellinger_select's contract (rows with sum <= 1, finite prices with |v| <= 1e6): every unlisted column j with
+ * a finite price and fixed row has C(i, j) - v[j] >= T, so the first out_proven[f][i] entries are the first entries of row i of the
+ * full exact reduced matrix of frame f ordered by (value, column), with exactly its values.  The float64 rounding of the one
+ * subtraction C - v is monotone (C <= C' implies fl(C - v) <= fl(C' - v)), so comparing rounded keys never inverts an order of
+ * true reduced costs across T, and its size (<= 2^-53 |v| <= 1.2e-10) lies in the slack pm_hellinger_list's contract already
+ * claims for |v| <= 1e6.  A larger kc proves more.  out_proven [n_frames][nA]; status1: one int32 (device), cleared by the call. */
+int pm_chi2_select_exact(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames, const double *v,
+                         const int32_t *cand_col, const double *cand_bound, int kc, int k, double delta, int32_t *out_col,
+                         double *out_cost, double *out_twin, int32_t *out_proven, int32_t *status1, void *stream);
+
 /* Listed entries of one pairing's two EXACT matrices (the bits of pm_chi2_cost_pair_sym's): out_natural[e], out_rolled[e] =
  * entry (rows[e], cols[e]) of the natural-order matrix (U11, U12, U13, U14 for pairing 0..3) and of its rolled-order twin (U22,
  * U21, U24, U23).  rows / cols / outputs: device, n_entries each; an index out of range yields NaN in both outputs.  What turns

@@ -566,6 +566,62 @@ def chi2_entries(sc_m1, sc_f1, pairing, rows, cols, trusted=False):
     return out[0], out[1]
 
 
+def chi2_select_exact(sc_a, sc_b, cand_cols, cand_bound, v=None, k=8, delta=None, twin=False, info=None):
+    """Exact rescoring of hellinger_select's candidate lists in one launch (pm_chi2_select_exact; csrc/pm_chi2_select.hip).
+    sc_a [N, 360], sc_b [F, M, 360] (or [M, 360]: F = 1), v [F, M] or None: as for hellinger_select; cand_cols int32 / cand_bound
+    float64 [F, N, kc]: what hellinger_select(k=kc) returned (the BOUND beside each column); 1 <= k <= kc <= 64; delta: the error
+    bound of the lists' bound (default hellinger_delta()).
+    -> (cols int32 [F, N, k], cost float64 [F, N, k], proven int32 [F, N]) (+ twin float64 [F, N, k] with twin=True): per (frame,
+    row) the k candidates of smallest key = cost - v[f, col] ascending by (key, column), cost UNREDUCED with chi2_cost's bits (twin:
+    the same terms summed in rolled order, chi2_entries' second output where the frames are the phi permutations of frame 1);
+    -1 / +inf where the list holds fewer candidates, -1 / NaN for a non-finite row of sc_a.  The first proven[f, i] entries are
+    PROVEN to be the first entries of row i of the full exact reduced matrix ordered by (value, column): their key lies strictly
+    below (bound[kc-1] - v[col[kc-1]]) - delta, which every unlisted column's exact reduced cost reaches (+inf when the list ends
+    in -1: it then holds every listable column).  info (dict): receives 'status' (bit 0: a non-finite moving row's unit; bit 1:
+    a candidate outside [-1, M), treated as absent; synchronises)."""
+    torch = _t()
+    a = _desc(sc_a, "sc_a")
+    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
+            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
+        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
+    _here(sc_b, "sc_b")
+    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
+    N, M = a.shape[0], sc_b.shape[-2]
+    if not (nat.is_torch(cand_cols) and cand_cols.is_cuda and cand_cols.dtype == torch.int32 and cand_cols.is_contiguous()
+            and cand_cols.dim() == 3 and tuple(cand_cols.shape[:2]) == (F, N) and 1 <= cand_cols.shape[2] <= 64):
+        raise ValueError("cand_cols must be a contiguous int32 GPU tensor [%d, %d, kc] with kc = 1..64" % (F, N))
+    kc, k = cand_cols.shape[2], int(k)
+    if not (nat.is_torch(cand_bound) and cand_bound.is_cuda and cand_bound.dtype == torch.float64 and cand_bound.is_contiguous()
+            and cand_bound.shape == cand_cols.shape):
+        raise ValueError("cand_bound must be a contiguous float64 GPU tensor of cand_cols' shape")
+    _here(cand_cols, "cand_cols"), _here(cand_bound, "cand_bound")
+    if not 1 <= k <= kc:
+        raise ValueError("k must be 1..kc (%d)" % kc)
+    delta = hellinger_delta() if delta is None else float(delta)
+    if not delta >= 0.0:
+        raise ValueError("delta must be >= 0")
+    if v is not None:
+        _here(_vec(v, F * M, "v"), "v")
+    cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
+    cost = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
+    tw = torch.empty((F, N, k), dtype=torch.float64, device=a.device) if twin else None
+    proven = torch.empty((F, N), dtype=torch.int32, device=a.device)
+    status = torch.empty(1, dtype=torch.int32, device=a.device)
+    check(nat.load().pm_chi2_select_exact(ptr(a), N, ptr(sc_b), M, M * NBINS, F, ptr(v), ptr(cand_cols), ptr(cand_bound), kc, k, delta,
+                                          ptr(cols), ptr(cost), ptr(tw), ptr(proven), ptr(status), nat.stream_ptr()))
+    if info is not None:
+        info["status"] = int(status.item())
+    return (cols, cost, proven, tw) if twin else (cols, cost, proven)
+
+
+def chi2_nearest(sc_a, sc_b, v=None, k=8, candidates=32, twin=False, split=0, info=None):
+    """The exact k nearest columns per row under column prices, with a proof, without a matrix: hellinger_select(k=candidates)
+    followed by chi2_select_exact on its lists (no host synchronisation in between) -> chi2_select_exact's result.  More
+    candidates prove more; candidates = 1..64, k <= candidates.  info (dict): receives 'status' (synchronises)."""
+    cand_cols, cand_bound = hellinger_select(sc_a, sc_b, v=v, k=candidates, split=split)
+    return chi2_select_exact(sc_a, sc_b, cand_cols, cand_bound, v=v, k=k, twin=twin, info=info)
+
+
 def _sym_workspace(lib, nM, nF, device):
     """Device scratch of the half-cost kernel's term table (the integer counts behind the descriptor values; include/platymatch_hip.h)."""
     return _t().empty(int(lib.pm_chi2_sym_workspace_bytes(nM, nF)), dtype=_t().uint8, device=device)

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libplatymatch_hip.so")
-SOURCES = ["pm_api.hip", "pm_stats.hip", "pm_shape_context.hip", "pm_chi2.hip", "pm_hellinger.hip", "pm_transform.hip",
+SOURCES = ["pm_api.hip", "pm_stats.hip", "pm_shape_context.hip", "pm_chi2.hip", "pm_chi2_select.hip", "pm_hellinger.hip", "pm_transform.hip",
            "pm_icp.hip", "pm_icp_grid.hip", "pm_similar.hip", "pm_ransac.hip", "pm_eval.hip", "pm_lsap_dev.hip", "pm_lsap_resident.hip", "pm_lsap.cpp", "pm_lsap_core.cpp",
            "pm_host_rng.cpp"]
 ARCH = "gfx950"
@@ -24,7 +24,9 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-ffp-contract=
          "-fgpu-rdc" if False else "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 # per-file additions.  pm_hellinger.hip: its float32 work belongs to the matrix cores; the few scalar float32 operations around
 # them are not to be fused into packed ones (the filter build's packed arithmetic is written by hand where it is wanted).
-EXTRA_FLAGS = {"pm_hellinger.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# pm_chi2_select.hip: float64 and integers throughout, nothing to pack; the same switch keeps it that way.
+_NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"pm_hellinger.hip": _NO_PACKED_F32, "pm_chi2_select.hip": _NO_PACKED_F32}
 
 
 def _hipcc():

@@ -249,6 +249,32 @@ def unary_distance_candidates(sc_moving, unary_fixed, k=16, col_offsets=None):
     return nat.like_input(cols, sc_moving), nat.like_input(lower, sc_moving)
 
 
+def unary_distance_nearest(sc_moving, unary_fixed, k=8, candidates=32, col_offsets=None, twin=False):
+    """Per moving nucleus its k nearest fixed nuclei with their EXACT distances and a proof, WITHOUT building a cost matrix:
+    unary_distance_candidates' lists (the Hellinger lower bound, `candidates` columns per row) rescored exactly in one kernel
+    (K.chi2_nearest).  sc_moving, unary_fixed, col_offsets: as for unary_distance_candidates; NumPy or torch in, the same kind out.
+    -> (cols int32 [F, N, k], dist float64 [F, N, k], proven int32 [F, N]) (+ twin float64 [F, N, k] with twin=True: the same
+    terms summed in the rolled bin order, the twin hypothesis' value where frames 2..4 are the phi permutations of frame 1).
+    dist[f, i, r] is exactly get_unary_distance(sc_moving[i], unary_fixed[f][cols[f, i, r]]), bit for bit; a row is ordered by
+    (dist - col_offsets[f, col], column) ascending, dist itself is returned unreduced.
+    GUARANTEE (descriptor rows that sum to at most 1, as get_unary's do; finite offsets up to 1e6 in size): the first proven[f, i]
+    columns of row i are THE fixed nuclei of smallest get_unary_distance(a_i, b_j) - col_offsets[f, j] among all M of frame f
+    (columns with a NaN or infinite offset aside), in order, ties by column.  Entries past proven[f, i] are exact values of good
+    candidates, but a column that was not listed may lie between them.  More `candidates` (up to 64) prove more: every unlisted
+    column is known to cost at least the last candidate's lower bound, and a longer list moves that threshold up.
+    cols -1 with dist +inf where fewer than k columns exist; -1 with NaN and proven 0 for a moving row holding a NaN."""
+    torch = nat.torch_mod()
+    a = nat.to_dev(sc_moving)
+    if _stacked(unary_fixed, len(unary_fixed)) or (nat.is_torch(unary_fixed) and unary_fixed.dim() == 2) or \
+            (isinstance(unary_fixed, np.ndarray) and unary_fixed.ndim == 2):
+        f = nat.to_dev(unary_fixed, dev=a.device)
+    else:
+        f = torch.stack([nat.to_dev(x, dev=a.device) for x in unary_fixed])
+    v = None if col_offsets is None else nat.to_dev(col_offsets, dev=a.device).reshape(-1)
+    out = K.chi2_nearest(a.contiguous(), f.contiguous(), v=v, k=k, candidates=candidates, twin=twin)
+    return tuple(nat.like_input(x, sc_moving) for x in out)
+
+
 def unary_distance_below(sc_moving, unary_fixed, threshold, row_offsets=None, col_offsets=None, exclude=None, cap=None):
     """Every pair (moving nucleus i, fixed nucleus j) that CAN have get_unary_distance(a_i, b_j) - row_offsets[i] - col_offsets[j]
     <= threshold, WITHOUT building a cost matrix: the Hellinger lower bound of unary_distance_candidates against a threshold

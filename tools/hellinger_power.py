@@ -4,7 +4,7 @@ with the product's own kernels — the two kill criteria of VERDICT.md "Next rou
   (i)  share of rows whose MATCHED column (the exact mode's assignment) lies inside the bound's top-k of the row;
   (ii) share of a row's columns whose bound lies below the row's 16th-smallest EXACT cost (what a per-row threshold cannot prune).
 Per pairing (U11, U12, U13, U14), for k = 16, 32, 64, plus the largest |L~ - L_float64| seen on sampled rows.
-Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel] [--list] [--select]
+Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-kernel] [--list] [--select] [--nearest]
   --rows R       criteria on R evenly spaced rows instead of all (50 000 nuclei: the exact matrix of R rows at a time)
   --speed        also time hellinger_topk(k=16, four frames) against chi2_filter4(float32) + pm_lsap_row_select_f32(k=16) on the
                  four matrices: alternating, seven repetitions each after a warm-up, HIP events around work that ends in a synchronise
@@ -14,6 +14,10 @@ Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-ke
                  of a matrix-free pricing round: entries listed per row under the final duals of the exact mode's device solve
   --select       the priced selection (K.hellinger_select) and nothing else: its speed against hellinger_topk(k=16) at k = 16 and
                  k = 8, with v = 0 and with v = the bound's column minima (alternating, seven repetitions each after a warm-up)
+  --nearest      the exact rescoring (K.chi2_select_exact) and nothing else: from the same hellinger_select(k=32) lists, F = 4, k = 8,
+                 the one-launch kernel against the same answer by the chain a resident-matrix selector runs (mask, gathers,
+                 K.chi2_entries per pairing, scatter, price gather, argsort, gathers), with v = 0 and v = the bound's column minima
+                 (alternating, seven repetitions each after a warm-up), and the share of units with proven == k
 Prints to stdout; writes nothing."""
 import argparse
 import os
@@ -33,6 +37,7 @@ def main():
     ap.add_argument("--only-kernel", action="store_true")
     ap.add_argument("--list", action="store_true")
     ap.add_argument("--select", action="store_true")
+    ap.add_argument("--nearest", action="store_true")
     args = ap.parse_args()
     import torch
     import bench
@@ -67,6 +72,10 @@ def main():
 
     if args.select:
         select_leg(torch, K, a, sc_f, n, timed)
+        return
+
+    if args.nearest:
+        nearest_leg(torch, K, a, sc_f, n, timed)
         return
 
     if args.speed:
@@ -195,6 +204,51 @@ def select_leg(torch, K, a, sc_f, n, timed):
     for (name, _), t in zip(legs, times):
         print("speed  %-46s median %8.2f ms  min %8.2f  max %8.2f  %6.1f TFLOP/s  (7 repetitions, alternating)"
               % (name, np.median(t), min(t), max(t), flop / np.median(t) / 1e9))
+
+
+def nearest_leg(torch, K, a, sc_f, n, timed, candidates=32, k=8):
+    zero = torch.zeros((4, n), dtype=torch.float64, device=a.device)
+    vmin = torch.stack([K.hellinger_topk(sc_f[f].contiguous(), a, k=1)[1][0, :, 0] for f in range(4)]).contiguous()
+    b1 = sc_f[0].contiguous()
+    rows_all = torch.arange(n, dtype=torch.int32, device=a.device)[:, None].expand(n, candidates)
+
+    def chain(lists, v):
+        """lsap.FilteredMatrix._row_select_t's steps around K.chi2_entries, pairing by pairing, cut to k"""
+        out_c, out_x = [], []
+        for f in range(4):
+            cols = lists[0][f]
+            valid = cols >= 0
+            exact = K.chi2_entries(a, b1, f, rows_all[valid].contiguous(), cols[valid].contiguous(), trusted=True)[0]
+            costs = torch.full(cols.shape, float("inf"), dtype=torch.float64, device=cols.device)
+            costs[valid] = exact
+            red = costs - v[f][cols.clamp(min=0).long()]
+            order = torch.argsort(torch.where(valid, red, torch.full_like(red, float("inf"))), dim=1, stable=True)[:, :k]
+            out_c.append(torch.gather(cols, 1, order)), out_x.append(torch.gather(costs, 1, order))
+        torch.cuda.synchronize()
+        return torch.stack(out_c), torch.stack(out_x)
+
+    def kernel(lists, v):
+        out = K.chi2_select_exact(a, sc_f, lists[0], lists[1], v=v, k=k)
+        torch.cuda.synchronize()
+        return out
+    legs = []
+    for name, v in (("v = 0", zero), ("v = column minima", vmin)):
+        lists = K.hellinger_select(a, sc_f, v=v, k=candidates)
+        legs.append(("chain around chi2_entries (%s)" % name, lambda lists=lists, v=v: chain(lists, v)))
+        legs.append(("chi2_select_exact (%s)" % name, lambda lists=lists, v=v: kernel(lists, v)))
+    outs = [run() for _, run in legs]                     # warm-up; and both routes give the same answer
+    for i in (0, 2):
+        same = torch.equal(outs[i][0], outs[i + 1][0]) and torch.equal(outs[i][1].view(torch.int64), outs[i + 1][1].view(torch.int64))
+        full = (outs[i + 1][2] == k).float().mean().item()
+        print("nearest %-20s columns and cost bits of the two routes %s; units with proven == k: %.2f %%, mean proven %.2f of %d"
+              % (legs[i + 1][0][18:], "identical" if same else "DIFFER", 100.0 * full, outs[i + 1][2].float().mean().item(), k))
+    times = [[] for _ in legs]
+    for _ in range(7):
+        for t, (_, run) in zip(times, legs):
+            t.append(timed(run)[0])
+    for (name, _), t in zip(legs, times):
+        print("speed  %-46s median %8.2f ms  min %8.2f  max %8.2f  (7 repetitions, alternating; %d x %d, F = 4, candidates = %d, k = %d)"
+              % (name, np.median(t), min(t), max(t), n, n, candidates, k))
 
 
 if __name__ == "__main__":
