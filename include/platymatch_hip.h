@@ -383,6 +383,11 @@ int pm_chi2_cost_pair_sym_ws(const double *sc_m1, int nM, const double *sc_f1, i
  * may table further shells on their own: pm_chi2_sym_ws_report counts them.  Copies 300 bytes to the host and synchronises the
  * stream. */
 int pm_chi2_sym_table_info(const void *ws, int32_t *tabled30, int32_t *table_size, void *stream);
+/* Report (benchmarks, tests): seeded30[g] = 1 if the last *_ws launch on this workspace could take shell g's reciprocals from the
+ * count-sum table (seeded division): every value is count / total, BOTH clouds have the same total, and the shell's largest
+ * count of the moving cloud plus that of the fixed cloud is below nseed = table_size^2.  Launch-wide; a tile seeds such a shell
+ * only from its switch shell on (where it gives up its term table).  With unequal totals nothing is seeded.  Synchronises. */
+int pm_chi2_sym_seed_info(const void *ws, int32_t *seeded30, int32_t *nseed, void *stream);
 /* pm_chi2_cost8_sym_ws (pairing = -1: out = eight matrices) or pm_chi2_cost_pair_sym_ws (pairing = 0..3: out = two) with a
  * per-shell count of the tiles that served the shell from the table: tiles_tabled30 (device, 30 x uint32, may be NULL) is
  * INCREMENTED — the caller clears it — once per 16-row x 64-column tile and shell; the launch has ceil(nM/16) * ceil(nF/64)

@@ -323,6 +323,10 @@ def chi2_cost8_frame1(sc_m1, sc_f1, out=None, info=None):
         check(lib.pm_chi2_sym_table_info(ptr(ws), ctypes.addressof(tabled), ctypes.addressof(size), nat.stream_ptr()))
         info["tabled_shells"] = [int(x) for x in tabled]
         info["table_size"] = int(size.value)
+        seeded, nseed = (ctypes.c_int32 * 30)(), ctypes.c_int32(0)
+        check(lib.pm_chi2_sym_seed_info(ptr(ws), ctypes.addressof(seeded), ctypes.addressof(nseed), nat.stream_ptr()))
+        info["seedable_shells"] = [int(x) for x in seeded]
+        info["nseed"] = int(nseed.value)
     return out
 
 
@@ -343,6 +347,22 @@ def chi2_frame1_tile_report(sc_m1, sc_f1, pairing=-1):
     check(lib.pm_chi2_sym_ws_report(ptr(a), nM, ptr(b), nF, t, ptr(out), out.stride(1), out.stride(0), ptr(ws), ws.numel(), ptr(tabled),
                                     nat.stream_ptr()))
     return out, tabled, ((nM + 15) // 16) * ((nF + 63) // 64)
+
+
+def chi2_frame1_seed_info(sc_m1, sc_f1):
+    """Which shells the half-cost kernel may divide with seeds from its count-sum table (pm_chi2_sym_seed_info after one
+    chi2_cost8_frame1 launch) -> (seeded, nseed): 30 flags, and the bound the shell's two largest counts must sum below."""
+    import ctypes
+    torch = _t()
+    a, b = _desc(sc_m1, "sc_m1"), _desc(sc_f1, "sc_f1")
+    nM, nF = a.shape[0], b.shape[0]
+    out = big_empty((8, nM, nF), torch.float64, a.device)
+    lib = nat.load()
+    ws = _sym_workspace(lib, nM, nF, a.device)
+    check(lib.pm_chi2_cost8_sym_ws(ptr(a), nM, ptr(b), nF, ptr(out), out.stride(1), out.stride(0), ptr(ws), ws.numel(), nat.stream_ptr()))
+    seeded, nseed = (ctypes.c_int32 * 30)(), ctypes.c_int32(0)
+    check(lib.pm_chi2_sym_seed_info(ptr(ws), ctypes.addressof(seeded), ctypes.addressof(nseed), nat.stream_ptr()))
+    return [int(x) for x in seeded], int(nseed.value)
 
 
 def chi2_cost8_relaxed(sc_m1, sc_f1, out=None, variant=1):

@@ -94,6 +94,7 @@ SIGNATURES = {
     "pm_chi2_cost_pair_sym": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_size_t, _c_size_t, _c_void_p]),
     "pm_chi2_sym_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
     "pm_chi2_sym_table_info": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "pm_chi2_sym_seed_info": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "pm_chi2_relaxed_workspace_bytes": (_c_size_t, [_c_int, _c_int]),
     "pm_chi2_relaxed_delta": (_c_double, []),
     "pm_chi2_filter_workspace_bytes": (_c_size_t, [_c_int, _c_int]),

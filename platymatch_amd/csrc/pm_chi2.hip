@@ -204,7 +204,33 @@ struct SymMeta {
     int bad;                           // some value is not fl(count / total): no table
     int pad;
     int maxc[2][CH_NSHELL];            // largest count per (r, theta) shell, saturated at 255
+    unsigned short maxfull[2][CH_NSHELL];   // the same, saturated at 65 535 (seeded division: the sum of the two must stay below NSEED)
 };
+
+// SEEDED DIVISION (NSP > 0).  When both clouds have the same total T, a computed term's denominator fl(fl(ca/T) + fl(cb/T)) is
+// (s/T)(1 + 3 * 2^-53) with s = ca + cb, so a ONE-dimensional table R[s] = fl(T/s) seeds the reciprocal to 2^-51 and one Newton
+// step finishes it (pm_common.h: div_seeded, seed_offset): fma(index), ds_read_b64, fma, fma instead of v_rcp_f64, fma, fma, fma —
+// 11 VALU instructions at 4 issue cycles against 12 of which the reciprocal takes 16.  Same quotient bits: both reciprocals are
+// accurate enough for the residual correction to round correctly (seed_div_check.hip).  R overlays the term table: shell g may
+// be seeded iff meta->bad == 0, tot[0] == tot[1] and maxfull[0][g] + maxfull[1][g] < NSEED = TL * TL (launch-wide); a tile serves
+// shells below its switch shell g_sw as before (tabled where its mask says so, div_pos otherwise), refills `tab` with R at g_sw
+// between two barriers, and from there on serves eligible shells seeded and the others by div_pos; nothing is tabled from g_sw
+// on.  g_sw minimises the summed per-shell cost under the constants below (ties: the larger g_sw, i.e. the table is kept).
+// With unequal totals nothing is eligible, g_sw = CH_STAGES, and the kernel runs exactly as without NSP.  NSP = 4: every pairing
+// of a seeded shell goes through R; NSP = 2: pairings 0 and 1 do, 2 and 3 stay on div_pos (less LDS gather traffic, more VALU).
+// issue cycles per (pair, bin) of a shell: computed from the instruction model (12 VALU, the reciprocal at 16 cycles, four pairings);
+// tabled and seeded as measured against it (0.353 and 0.898 of a computed shell: tools/seeded_shell_cost.py,
+// profiles/seeded_shell_cost.txt; the seeded model said 176)
+constexpr int CH_COST_TABLED = 85, CH_COST_SEEDED = 216, CH_COST_COMPUTED = 240;
+// terms per software-pipelined part of a seeded (row, pairing) group: with 6 the 8-matrix kernel spills 42 registers, with 3 two,
+// with 2 none (254 of 256)
+constexpr int CH_SEED_PART = 2;
+constexpr int CH_NSP_DEFAULT = 4;      // pairings per row the product's kernel seeds (PM_CHI2_SEED in the environment: 0, 2 or 4)
+inline int seed_pairings() {
+    const char *e = getenv("PM_CHI2_SEED");                // (read per launch, as PM_CHI2_MAX_BLOCKS: a measurement and test knob)
+    if (e && e[0] && !e[1] && (e[0] == '0' || e[0] == '2' || e[0] == '4')) return e[0] - '0';
+    return CH_NSP_DEFAULT;
+}
 
 // RELAX (round 4, opt-in, never the default): the same eight matrices WITHOUT the bit-identity contract — an experiment on what
 // the exact formulation costs.  (a-b)^2/(a+b) = (a+b) - 4ab/(a+b), so
@@ -223,7 +249,12 @@ __device__ __forceinline__ double relaxed_recip(double s) {
     return __builtin_fma(r, e, r);
 }
 
-template <int SY_RI, int MINW, int TSEL = -1, int TL = 0, bool RELAX = false>   // rows per wave; min waves per SIMD for the register allocator; pairing; table size; relaxed arithmetic
+// PSEL: -1 = the four pairings, 0..3 = one pairing.  The product's instantiations (CH_TL table, exact arithmetic, four rows per wave,
+// two waves per SIMD) seed CH_NSP_DEFAULT pairings, all others none.  The measurement knob (PM_CHI2_SEED) reaches the other
+// settings through further PSEL codes, so that the kernel keeps its five parameters and the product kernel its name (profiles,
+// the register-budget test): -2 = four pairings, the non-default one of 2 / 4 seeded; -3 = four pairings, none seeded;
+// 4..7 = pairing PSEL - 4, not seeded.
+template <int SY_RI, int MINW, int PSEL = -1, int TL = 0, bool RELAX = false>   // rows per wave; min waves per SIMD for the register allocator; pairing (and seeding code); table size; relaxed arithmetic
 __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double *__restrict__ scA, int nA,
                                                                  const double *__restrict__ scB, int nB,
                                                                  double *__restrict__ out, size_t ld, size_t mstride,
@@ -234,6 +265,10 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
                                                                  const double *__restrict__ sumA = nullptr,
                                                                  const double *__restrict__ sumB = nullptr,
                                                                  unsigned int *__restrict__ report = nullptr) {
+    constexpr int TSEL = (PSEL >= 4) ? PSEL - 4 : (PSEL < -1) ? -1 : PSEL;
+    constexpr bool SEEDABLE = SY_RI == 4 && MINW == 2 && TL == CH_TL && !RELAX;
+    constexpr int NSP = !SEEDABLE ? 0 : (PSEL == -1 || (PSEL >= 0 && PSEL < 4)) ? CH_NSP_DEFAULT : (PSEL == -2) ? 6 - CH_NSP_DEFAULT : 0;
+    static_assert(PSEL >= -3 && PSEL <= 7 && (SEEDABLE || (PSEL >= -1 && PSEL < 4)), "pairing code");
     constexpr int SY_TI = 4 * SY_RI;      // rows per tile
     __shared__ __attribute__((aligned(16))) double A_s[SY_TI][CH_K];
     __shared__ __attribute__((aligned(16))) double B_s[CH_TJ][CH_BPITCH];
@@ -257,6 +292,9 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
         for (int h = 0; h < NACC; ++h) acc[r][h] = 0.0;
 
     unsigned int tabmask = 0;             // shells this TILE serves from the table (uniform over the workgroup)
+    unsigned int seedmask = 0;            // shells this tile divides with seeds out of R (all at or above g_sw)
+    int g_sw = 0, seed_n = 0;             // the switch shell; entries of R to fill
+    static_assert(NSP == 0 || (TL > 0 && !RELAX && (NSP == 2 || NSP == 4)), "seeds overlay the exact kernel's term table");
     if constexpr (TL > 0) {
         static_assert(TL <= 128 && CH_STAGES < 32, "the packed byte test below; one mask bit per shell");
         __shared__ unsigned int over_s;   // shells in which a row or a column of this tile holds a count >= TL
@@ -315,6 +353,33 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
             }
         }
         tabmask = __builtin_amdgcn_readfirstlane(tabmask);
+        if constexpr (NSP > 0) {
+            // launch-wide eligibility, then the switch shell: cost(k) = shells below k as the mask says, shells from k on seeded
+            // or computed; all of it wave-uniform (scalar loads of the header, scalar arithmetic)
+            int smax = 0;
+            if (meta->bad == 0 && meta->tot[0] == meta->tot[1]) {
+                for (int g = 0; g < CH_STAGES; ++g) {
+                    const int s = (int)meta->maxfull[0][g] + (int)meta->maxfull[1][g];
+                    if (s < TL * TL) {
+                        seedmask |= 1u << g;
+                        smax = max(smax, s);
+                    }
+                }
+            }
+            int cost = 0;
+            for (int g = 0; g < CH_STAGES; ++g) cost += ((seedmask >> g) & 1u) ? CH_COST_SEEDED : CH_COST_COMPUTED;
+            int best = cost;
+            for (int k = 1; k <= CH_STAGES; ++k) {
+                cost += (((tabmask >> (k - 1)) & 1u) ? CH_COST_TABLED : CH_COST_COMPUTED) -
+                        (((seedmask >> (k - 1)) & 1u) ? CH_COST_SEEDED : CH_COST_COMPUTED);
+                if (cost <= best) best = cost, g_sw = k;
+            }
+            g_sw = __builtin_amdgcn_readfirstlane(g_sw);
+            const unsigned int below = (g_sw >= 32) ? ~0u : (1u << g_sw) - 1u;
+            tabmask &= below;             // (before the report: a shell tabled by the mask but past the switch is NOT tabled here)
+            seedmask = __builtin_amdgcn_readfirstlane(seedmask & ~below);
+            seed_n = __builtin_amdgcn_readfirstlane(smax + 1);
+        }
         if (report && tid < CH_STAGES && ((tabmask >> tid) & 1u)) atomicAdd(&report[tid], 1u);
         if (tabmask) __syncthreads();
     }
@@ -363,7 +428,18 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
         if (g0 < CH_STAGES) prefetch(g0);
     }
 
+    // the seed table's LDS address folded into the index constant (seed_offset): the gather's address costs one fma
+    const unsigned int tab_lds = (unsigned int)(uintptr_t)(__attribute__((address_space(3))) double *)tab;
+    const double seed_T = (NSP > 0) ? meta->tot[0] : 0.0;
+    const double seed_magic = __longlong_as_double((long long)((0x430ull << 52) | tab_lds));   // 2^49 + tab_lds / 8, in scalar registers
     for (int g = 0; g < CH_STAGES; ++g) {
+        if constexpr (NSP > 0) {
+            if (g == g_sw && seedmask) {
+                __syncthreads();          // the last tabled stage of every wave has read the term table
+                for (int e = tid; e < seed_n; e += CH_THREADS) tab[e] = e ? div_pos(seed_T, (double)e) : 1.0;
+                // (published by the two barriers of the staging below: shell g_sw is not tabled)
+            }
+        }
         if constexpr (TL > 0) {
             if ((tabmask >> g) & 1u) {
                 // this lane's twelve fixed counts of the shell, as byte offsets into a table row
@@ -477,6 +553,64 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
         for (int k = 0; k < CH_K; k += 2) {
             double2 v = *reinterpret_cast<const double2 *>(&B_s[lane][k]);
             b[k] = v.x; b[k + 1] = v.y;
+        }
+        if constexpr (NSP > 0) {
+            if ((seedmask >> g) & 1u) {
+                // the seeded stage: staging, pairings and running-sum order of the computed stage below; a (row, pairing)
+                // group's twelve index fmas and gathers are issued ahead of the previous group's arithmetic (as the tabled stage)
+                constexpr int NT = (TSEL < 0) ? 4 : 1;
+#pragma unroll
+                for (int r = 0; r < SY_RI; ++r) {
+                    double a[CH_K];
+#pragma unroll
+                    for (int k = 0; k < CH_K; k += 2) {
+                        double2 v = *reinterpret_cast<const double2 *>(&A_s[wave * SY_RI + r][k]);
+                        a[k] = v.x; a[k + 1] = v.y;
+                    }
+                    // part groups of HK terms: h = NP * (pairing slot) + part; the next part's gathers fly under this part's arithmetic
+                    constexpr int HK = CH_SEED_PART, NP = CH_K / HK;
+                    double Rc[HK], Rn[HK], T[CH_K];
+                    auto gather = [&](int h, double (&R)[HK]) {
+                        const int t = (TSEL < 0) ? h / NP : TSEL;
+#pragma unroll
+                        for (int k = 0; k < HK; ++k) {
+                            const int p = (h % NP) * HK + k;
+                            const int q = (t == 0) ? p : (t == 1) ? (p + 6) % 12 : (t == 2) ? 11 - p : (17 - p) % 12;
+                            R[k] = *(const __attribute__((address_space(3))) double *)(uintptr_t)seed_offset(a[p] + b[q], seed_T, seed_magic);
+                        }
+                    };
+                    gather(0, Rc);
+#pragma unroll
+                    for (int h = 0; h < NP * NT; ++h) {
+                        const int i = h / NP, t = (TSEL < 0) ? i : TSEL;
+                        const bool seeded = TSEL >= 0 || i < NSP, next_seeded = h + 1 < NP * NT && (TSEL >= 0 || (h + 1) / NP < NSP);
+                        if (next_seeded) gather(h + 1, Rn);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int k = 0; k < HK; ++k) {
+                            const int p = (h % NP) * HK + k;
+                            const int q = (t == 0) ? p : (t == 1) ? (p + 6) % 12 : (t == 2) ? 11 - p : (17 - p) % 12;
+                            const double df = a[p] - b[q];
+                            T[p] = seeded ? div_seeded(df * df, a[p] + b[q], Rc[k]) : div_pos(df * df, a[p] + b[q]);
+                        }
+                        if (h % NP == NP - 1) {
+                            const int hn = (TSEL < 0) ? t : 0, hr = (TSEL >= 0) ? 1 : (t == 0) ? 5 : (t == 1) ? 4 : (t == 2) ? 7 : 6;
+                            double sn = acc[r][hn], sr = acc[r][hr];
+#pragma unroll
+                            for (int p = 0; p < CH_K; ++p) sn = sn + T[p];
+#pragma unroll
+                            for (int p = 0; p < CH_K; ++p) sr = sr + T[(p + 6) % 12];
+                            acc[r][hn] = sn;
+                            acc[r][hr] = sr;
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int k = 0; k < HK; ++k)
+                            if (next_seeded) Rc[k] = Rn[k];
+                    }
+                }
+                continue;
+            }
         }
 #pragma unroll
         for (int r = 0; r < SY_RI; ++r) {
@@ -741,7 +875,10 @@ __global__ void sym_meta_init_kernel(SymMeta *m) {
         m->tot[t] = 0.0;
     }
     if (t == 0) m->bad = 0, m->pad = 0;
-    if (t < CH_NSHELL) m->maxc[0][t] = m->maxc[1][t] = 0;
+    if (t < CH_NSHELL) {
+        m->maxc[0][t] = m->maxc[1][t] = 0;
+        m->maxfull[0][t] = m->maxfull[1][t] = 0;
+    }
 }
 
 // smallest positive value (count 1 of some bin, in any cloud with a singly occupied bin: 1 / total); anything that is not a
@@ -779,8 +916,8 @@ __global__ void counts_total_kernel(SymMeta *m) {
 // cloud, the 64 lanes of a wave queuing on five or six addresses).
 __global__ __launch_bounds__(256) void counts_extract_kernel(const double *__restrict__ sc, size_t n_groups, unsigned char *__restrict__ cnt,
                                                              SymMeta *m, int which) {
-    __shared__ int smax[CH_NSHELL];
-    if (threadIdx.x < CH_NSHELL) smax[threadIdx.x] = 0;
+    __shared__ int smax[CH_NSHELL], sfull[CH_NSHELL];
+    if (threadIdx.x < CH_NSHELL) smax[threadIdx.x] = sfull[threadIdx.x] = 0;
     __syncthreads();
     const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (g < n_groups) {
@@ -790,7 +927,7 @@ __global__ __launch_bounds__(256) void counts_extract_kernel(const double *__res
 #pragma unroll
         for (int k = 0; k < CH_K / 2; ++k) { const double2 t = src[k]; v[2 * k] = t.x; v[2 * k + 1] = t.y; }
         unsigned int packed[CH_K / 4] = {0u, 0u, 0u};
-        int top = 0;
+        int top = 0, topfull = 0;
         bool all_ok = true;
 #pragma unroll
         for (int k = 0; k < CH_K; ++k) {
@@ -800,15 +937,29 @@ __global__ __launch_bounds__(256) void counts_extract_kernel(const double *__res
             const int cc = ok ? (int)min(c, 255.0) : 255;
             packed[k >> 2] |= (unsigned int)cc << (8 * (k & 3));
             top = max(top, cc);
+            topfull = max(topfull, ok ? (int)min(c, 65535.0) : 65535);
         }
         if (!all_ok) atomicOr(&m->bad, 1);
         unsigned int *dst = reinterpret_cast<unsigned int *>(cnt + g * CH_K);
         dst[0] = packed[0]; dst[1] = packed[1]; dst[2] = packed[2];
         atomicMax(&smax[(int)(g % CH_NSHELL)], top);
+        if (topfull > 255) atomicMax(&sfull[(int)(g % CH_NSHELL)], topfull);      // (below that, top says it)
     }
     __syncthreads();
-    if (threadIdx.x < CH_NSHELL && smax[threadIdx.x] > 0) atomicMax(&m->maxc[which][threadIdx.x], smax[threadIdx.x]);
+    if (threadIdx.x < CH_NSHELL && smax[threadIdx.x] > 0) {
+        atomicMax(&m->maxc[which][threadIdx.x], smax[threadIdx.x]);
+        // maxfull: a 16-bit maximum inside its 32-bit word (no 16-bit atomics), by compare-and-swap; most blocks find it there already
+        const unsigned int v = (unsigned int)max(smax[threadIdx.x], sfull[threadIdx.x]), sh = 16u * (threadIdx.x & 1u);
+        unsigned int *w = reinterpret_cast<unsigned int *>(m->maxfull[which]) + (threadIdx.x >> 1);
+        unsigned int old = __atomic_load_n(w, __ATOMIC_RELAXED);
+        while (((old >> sh) & 0xffffu) < v) {
+            const unsigned int seen = atomicCAS(w, old, (old & ~(0xffffu << sh)) | (v << sh));
+            if (seen == old) break;
+            old = seen;
+        }
+    }
 }
+static_assert(offsetof(SymMeta, maxfull) % 4 == 0 && (CH_NSHELL * sizeof(unsigned short)) % 4 == 0, "maxfull[which] starts on a dword");
 
 constexpr size_t SYM_META_BYTES = 512;
 static_assert(sizeof(SymMeta) <= SYM_META_BYTES, "workspace header");
@@ -834,6 +985,19 @@ int sym_prepare(const double *sc_m1, int nM, const double *sc_f1, int nF, void *
     counts_extract_kernel<<<(unsigned int)((gB + 255) / 256), 256, 0, s>>>(sc_f1, gB, w.cntB, w.meta, 1);
     return launch_status();
 }
+
+// the product's kernel (CH_TL table, two waves per SIMD) with nsp = 0, 2 or 4 pairings per row on seeded division; a single
+// pairing (TSEL >= 0) is seeded or not.  (chi2_sym_kernel's PSEL codes)
+template <int TSEL>
+int sym_product_launch(int nsp, const double *sc_m1, int nM, const double *sc_f1, int nF, double *out, size_t ld, size_t mstride, hipStream_t s,
+                       const SymWs &w, unsigned int *report) {
+    constexpr int OFF = (TSEL < 0) ? -3 : TSEL + 4, OTHER = (TSEL < 0) ? -2 : TSEL;
+    if (nsp == 0)
+        return chi2_sym_launch<4, 2, OFF, CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, mstride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, report);
+    if (TSEL < 0 && nsp != CH_NSP_DEFAULT)
+        return chi2_sym_launch<4, 2, OTHER, CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, mstride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, report);
+    return chi2_sym_launch<4, 2, TSEL, CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, mstride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, report);
+}
 }  // namespace pm
 
 extern "C" size_t pm_chi2_sym_workspace_bytes(int nM, int nF) {
@@ -853,7 +1017,7 @@ extern "C" int pm_chi2_cost8_sym_ws_variant(const double *sc_m1, int nM, const d
     if (rc != PM_OK) return rc;
     switch (variant) {
         case 0: return pm::chi2_sym_launch<4, 2, -1, 64>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
-        case 1: return pm::chi2_sym_launch<4, 2, -1, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
+        case 1: return pm::sym_product_launch<-1>(pm::seed_pairings(), sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w, nullptr);
         case 2: return pm::chi2_sym_launch<4, 2>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s);
         case 3: return pm::chi2_sym_launch<4, 3, -1, 64>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
         case 4: return pm::chi2_sym_launch<4, 3, -1, 48>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta);
@@ -877,6 +1041,23 @@ extern "C" int pm_chi2_sym_table_info(const void *ws, int32_t *tabled30, int32_t
     for (int g = 0; g < pm::CH_NSHELL; ++g)
         tabled30[g] = (m.bad == 0 && m.maxc[0][g] < pm::CH_TL && m.maxc[1][g] < pm::CH_TL) ? 1 : 0;
     *table_size = pm::CH_TL;
+    return PM_OK;
+}
+
+// which shells the last *_ws launch on this workspace could divide with seeds (launch-wide; synchronises)
+extern "C" int pm_chi2_sym_seed_info(const void *ws, int32_t *seeded30, int32_t *nseed, void *stream) {
+    if (!ws || !seeded30 || !nseed) return PM_ERR_INVALID_ARG;
+    pm::SymMeta m;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(&m, ws, sizeof(m), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    {
+        pm::launch_status();
+        return PM_ERR_LAUNCH;
+    }
+    constexpr int NSEED = pm::CH_TL * pm::CH_TL;
+    for (int g = 0; g < pm::CH_NSHELL; ++g)
+        seeded30[g] = (m.bad == 0 && m.tot[0] == m.tot[1] && (int)m.maxfull[0][g] + (int)m.maxfull[1][g] < NSEED) ? 1 : 0;
+    *nseed = NSEED;
     return PM_OK;
 }
 
@@ -1006,12 +1187,13 @@ extern "C" int pm_chi2_sym_ws_report(const double *sc_m1, int nM, const double *
     const int rc = pm::sym_prepare(sc_m1, nM, sc_f1, nF, ws, ws_bytes, s, w);
     if (rc != PM_OK) return rc;
     unsigned int *rep = tiles_tabled30;
+    const int nsp = pm::seed_pairings();
     switch (pairing) {
-        case -1: return pm::chi2_sym_launch<4, 2, -1, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
-        case 0: return pm::chi2_sym_launch<4, 2, 0, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
-        case 1: return pm::chi2_sym_launch<4, 2, 1, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
-        case 2: return pm::chi2_sym_launch<4, 2, 2, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
-        default: return pm::chi2_sym_launch<4, 2, 3, pm::CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, rep);
+        case -1: return pm::sym_product_launch<-1>(nsp, sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w, rep);
+        case 0: return pm::sym_product_launch<0>(nsp, sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w, rep);
+        case 1: return pm::sym_product_launch<1>(nsp, sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w, rep);
+        case 2: return pm::sym_product_launch<2>(nsp, sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w, rep);
+        default: return pm::sym_product_launch<3>(nsp, sc_m1, nM, sc_f1, nF, out, ld, matrix_stride, s, w, rep);
     }
 }
 

@@ -62,4 +62,29 @@ __device__ __forceinline__ double div_pos(double n, double d) {
     return __builtin_fma(res, r, q);
 }
 
+// n / d as div_pos, with the reciprocal taken from a table instead of v_rcp_f64: for the chi-square denominators of two clouds
+// with ONE common total T.  d = fl(fl(ca/T) + fl(cb/T)) for integer counts ca, cb (a zero cb staged as 1e-300 adds nothing), so
+// d = (s/T)(1 + theta) with s = ca + cb and |theta| <= 3 * 2^-53 (two divisions' roundings, each weighted by its share of the sum,
+// and the addition's).  r0 = R[s] = fl(T/s) = (T/s)(1 + rho), |rho| <= 2^-53, is therefore a reciprocal of d with relative
+// error |1 - d r0| <= 4 * 2^-53 + O(2^-105) < 2^-51.  One Newton step r = r0 + r0 e, e = fl(1 - d r0) (exact up to its own
+// rounding of a quantity below 2^-51, i.e. to 2^-104), leaves a truncation error e^2 <= 2^-102 before r's rounding — tighter than
+// div_pos's 2^-73 after its cubic step — and the quotient gets the same exact-residual correction.  s = 0 (both counts zero:
+// d = 1e-300, n = 1e-600 = 0): R[0] = 1 gives r = 2, q = 0, res = 0, result +0 = 0 / 1e-300.  Checked bit for bit against IEEE
+// division over every (ca, cb) with ca + cb < 8 836 for several totals, on the device and on the host
+// (tools/microbench/seed_div_check.hip, run by the test-suite both ways).
+__device__ __forceinline__ double div_seeded(double n, double d, double r0) {
+    const double e = __builtin_fma(-d, r0, 1.0);
+    const double r = __builtin_fma(r0, e, r0);
+    const double q = n * r;
+    const double res = __builtin_fma(-d, q, n);
+    return __builtin_fma(res, r, q);
+}
+
+// Byte offset of R[s] for the denominator d above, in ONE instruction: m = fl(d T + 2^49) has an ulp of 1/8, and d T lies within
+// s * 2^-51 < 1/16 of the integer s (s < 2^13), so m = 2^49 + s exactly and the low dword of its bit pattern is 8 s.  `magic` is
+// 2^49 + base/8 for a table at the (8-byte aligned, < 2^16) address `base`: the low dword is then base + 8 s, the address itself.
+__device__ __forceinline__ unsigned int seed_offset(double d, double T, double magic = 0x1p49) {
+    return (unsigned int)__double2loint(__builtin_fma(d, T, magic));
+}
+
 }  // namespace pm

@@ -43,7 +43,8 @@ def main():
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
     rec = {"points": n, "reps": args.reps, "build_ms": {"min": min(ms), "median": float(np.median(ms)), "max": max(ms)},
-           "tabled_launch_wide": info.get("tabled_shells")}
+           "tabled_launch_wide": info.get("tabled_shells"), "seedable_launch_wide": info.get("seedable_shells"),
+           "seeded_pairings_env": os.environ.get("PM_CHI2_SEED")}
     if hasattr(K, "chi2_frame1_tile_report"):
         del U
         _, tabled, tiles = K.chi2_frame1_tile_report(sc_m[0], sc_f[0])
