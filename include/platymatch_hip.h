@@ -325,6 +325,22 @@ int pm_hellinger_select(const double *scA, int nA, const double *scB, int nB, si
                         int k, int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1, void *ws, size_t ws_bytes,
                         void *stream);
 
+/* PRICED SELECTION on the bf16 matrix path (csrc/pm_hellinger_bf16.hip: hl_select_bf16_kernel): pm_hellinger_select with every
+ * sqrt-descriptor split into two bf16 pieces and the product taken as hi.hi + hi.lo + lo.hi (v_mfma_f32_32x32x16_bf16), bins in
+ * index order, the three products of a 16-bin step in that order.  Arguments, outputs, tails, non-finite rows and prices, the
+ * key and its order: as for pm_hellinger_select, except k 1..32 (a larger k is PM_ERR_INVALID_ARG: pm_hellinger_select serves up
+ * to 64) and split: workgroups the fixed rows are divided over per panel of 256 moving rows, 0 = automatic (the result does not
+ * depend on it, bit for bit).
+ * CONTRACT: pm_hellinger_select's, word for word, with delta = pm_hellinger_delta_bf16 (a HOST function, as pm_hellinger_delta) in
+ * place of pm_hellinger_delta.  The bound bits are NOT those of pm_hellinger_topk / _list / _select: lists of the two precisions are
+ * each valid under their own delta and are not compared entry by entry.  pm_chi2_select_exact takes these lists with this delta.
+ * ws: pm_hellinger_select_bf16_workspace bytes, 16-byte aligned device memory. */
+size_t pm_hellinger_select_bf16_workspace(int nA, int nB, int n_frames, int k);
+int pm_hellinger_select_bf16(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames,
+                             const double *v, int k, int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1,
+                             void *ws, size_t ws_bytes, void *stream);
+int pm_hellinger_delta_bf16(double *delta1_host);
+
 /* EXACT RESCORING of such lists (csrc/pm_chi2_select.hip: chi2_select_kernel), the step from the bound to exact costs: every
  * candidate of every list is evaluated with the exact build's bits, each row is ordered by exact reduced cost, and the call
  * reports how many leading entries are PROVEN to be the row's true smallest.  One launch, no N x M matrix, no workspace.

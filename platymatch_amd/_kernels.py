@@ -461,7 +461,7 @@ def hellinger_topk(sc_a, sc_b, k=16, split=0, info=None):
     return cols, bound
 
 
-def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None):
+def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None, precision="f32"):
     """Per row of sc_a [N, 360] the k columns of each fixed frame sc_b [F, M, 360] (or [M, 360]: F = 1) with the smallest
     key = bound - v[f, j], the Hellinger lower bound reduced by column prices — an assignment solver's row_select(v, k) without a
     matrix (pm_hellinger_select; csrc/pm_hellinger.hip: hl_select_kernel).  v: float64 GPU tensor [F, M] (or [M] for F = 1), or
@@ -471,16 +471,22 @@ def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None):
     NaN or infinite is never listed.  With v None or all +0.0 the result is hellinger_topk's, bit for bit.  Exact cost - v >=
     key - hellinger_delta() for listed entries, >= key[..., -1] - hellinger_delta() for every other column with a finite price.
     split: workgroups per panel of 128 rows (0 = automatic; same bits for any value).  info (dict): receives 'nonfinite' (of the
-    descriptors; synchronises)."""
+    descriptors; synchronises).
+    precision='bf16x3': the same selection on the bf16 matrix path (pm_hellinger_select_bf16; csrc/pm_hellinger_bf16.hip: the
+    sqrt-descriptors split into two bf16 pieces, three products), k <= 32 (ValueError above), panels of 256 rows.  Every sentence
+    above holds with hellinger_delta('bf16x3') = 1.77e-4 in place of hellinger_delta() = 4.31e-5, EXCEPT the bit identities: the
+    bounds of the two precisions are not bit-compatible (each list is valid under its own delta)."""
     torch = _t()
+    _precision(precision)
     a = _desc(sc_a, "sc_a")
     if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
             and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
         raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
     _here(sc_b, "sc_b")
     k, split = int(k), int(split)
-    if not 1 <= k <= 64:
-        raise ValueError("k must be 1..64")
+    kmax = 64 if precision == "f32" else 32
+    if not 1 <= k <= kmax:
+        raise ValueError("k must be 1..%d with precision=%r" % (kmax, precision))
     if split < 0:
         raise ValueError("split must be >= 0 (0 = automatic)")
     F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
@@ -488,12 +494,14 @@ def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None):
     if v is not None:
         _here(_vec(v, F * M, "v"), "v")
     lib = nat.load()
+    size, call = ((lib.pm_hellinger_select_workspace, lib.pm_hellinger_select) if precision == "f32" else
+                  (lib.pm_hellinger_select_bf16_workspace, lib.pm_hellinger_select_bf16))
     cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
     bound = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
     flag = torch.empty(1, dtype=torch.int32, device=a.device)
-    ws = nat.workspace(lib.pm_hellinger_select_workspace(N, M, F, k), a.device)
-    check(lib.pm_hellinger_select(ptr(a), N, ptr(sc_b), M, M * NBINS, F, ptr(v), k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws),
-                                  ws.numel(), nat.stream_ptr()))
+    ws = nat.workspace(size(N, M, F, k), a.device)
+    check(call(ptr(a), N, ptr(sc_b), M, M * NBINS, F, ptr(v), k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws), ws.numel(),
+               nat.stream_ptr()))
     if info is not None:
         info["nonfinite"] = int(flag.item())
     return cols, bound
@@ -556,12 +564,20 @@ def hellinger_list(sc_a, sc_b, u, v, tau, skip=None, cap=None, split=0, info=Non
     return out
 
 
-def hellinger_delta():
+def _precision(precision):
+    if precision not in ("f32", "bf16x3"):
+        raise ValueError("precision must be 'f32' or 'bf16x3', not %r" % (precision,))
+
+
+def hellinger_delta(precision="f32"):
     """Absolute error bound of hellinger_topk's bounds against the float64 Hellinger bound, for descriptor rows that sum to at
-    most 1 (csrc/pm_hellinger.hip: PM_HELLINGER_DELTA)."""
+    most 1 (csrc/pm_hellinger.hip: PM_HELLINGER_DELTA = 4.31e-5); precision='bf16x3': that of hellinger_select(precision='bf16x3')
+    (csrc/pm_hellinger_bf16.hip: PM_HELLINGER_DELTA_BF16X3 = 1.77e-4)."""
     import ctypes
+    _precision(precision)
     d = ctypes.c_double(0.0)
-    check(nat.load().pm_hellinger_delta(ctypes.addressof(d)))
+    lib = nat.load()
+    check((lib.pm_hellinger_delta if precision == "f32" else lib.pm_hellinger_delta_bf16)(ctypes.addressof(d)))
     return float(d.value)
 
 
@@ -634,12 +650,14 @@ def chi2_select_exact(sc_a, sc_b, cand_cols, cand_bound, v=None, k=8, delta=None
     return (cols, cost, proven, tw) if twin else (cols, cost, proven)
 
 
-def chi2_nearest(sc_a, sc_b, v=None, k=8, candidates=32, twin=False, split=0, info=None):
+def chi2_nearest(sc_a, sc_b, v=None, k=8, candidates=32, twin=False, split=0, info=None, precision="f32"):
     """The exact k nearest columns per row under column prices, with a proof, without a matrix: hellinger_select(k=candidates)
     followed by chi2_select_exact on its lists (no host synchronisation in between) -> chi2_select_exact's result.  More
-    candidates prove more; candidates = 1..64, k <= candidates.  info (dict): receives 'status' (synchronises)."""
-    cand_cols, cand_bound = hellinger_select(sc_a, sc_b, v=v, k=candidates, split=split)
-    return chi2_select_exact(sc_a, sc_b, cand_cols, cand_bound, v=v, k=k, twin=twin, info=info)
+    candidates prove more; candidates = 1..64, k <= candidates.  info (dict): receives 'status' (synchronises).
+    precision='bf16x3': the candidate lists come from the bf16 matrix path (candidates <= 32) and are rescored under ITS delta,
+    hellinger_delta('bf16x3'); the exact values are the same bits, the larger delta can only lower `proven`."""
+    cand_cols, cand_bound = hellinger_select(sc_a, sc_b, v=v, k=candidates, split=split, precision=precision)
+    return chi2_select_exact(sc_a, sc_b, cand_cols, cand_bound, v=v, k=k, delta=hellinger_delta(precision), twin=twin, info=info)
 
 
 def _sym_workspace(lib, nM, nF, device):

@@ -111,6 +111,10 @@ SIGNATURES = {
     "pm_hellinger_select_workspace": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
     "pm_hellinger_select": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_size_t, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p,
                                      _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "pm_hellinger_select_bf16_workspace": (_c_size_t, [_c_int, _c_int, _c_int, _c_int]),
+    "pm_hellinger_select_bf16": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_size_t, _c_int, _c_void_p, _c_int, _c_int, _c_void_p,
+                                          _c_void_p, _c_void_p, _c_void_p, _c_size_t, _c_void_p]),
+    "pm_hellinger_delta_bf16": (_c_int, [_c_void_p]),
     "pm_chi2_select_exact": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_size_t, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_int,
                                       _c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "pm_chi2_entries_sym": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libplatymatch_hip.so")
-SOURCES = ["pm_api.hip", "pm_stats.hip", "pm_shape_context.hip", "pm_chi2.hip", "pm_chi2_select.hip", "pm_hellinger.hip", "pm_transform.hip",
+SOURCES = ["pm_api.hip", "pm_stats.hip", "pm_shape_context.hip", "pm_chi2.hip", "pm_chi2_select.hip", "pm_hellinger.hip", "pm_hellinger_bf16.hip", "pm_transform.hip",
            "pm_icp.hip", "pm_icp_grid.hip", "pm_similar.hip", "pm_ransac.hip", "pm_eval.hip", "pm_lsap_dev.hip", "pm_lsap_resident.hip", "pm_lsap.cpp", "pm_lsap_core.cpp",
            "pm_host_rng.cpp"]
 ARCH = "gfx950"
@@ -26,7 +26,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-ffp-contract=
 # them are not to be fused into packed ones (the filter build's packed arithmetic is written by hand where it is wanted).
 # pm_chi2_select.hip: float64 and integers throughout, nothing to pack; the same switch keeps it that way.
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"pm_hellinger.hip": _NO_PACKED_F32, "pm_chi2_select.hip": _NO_PACKED_F32}
+EXTRA_FLAGS = {"pm_hellinger.hip": _NO_PACKED_F32, "pm_hellinger_bf16.hip": _NO_PACKED_F32, "pm_chi2_select.hip": _NO_PACKED_F32}
 
 
 def _hipcc():

@@ -211,7 +211,7 @@ def unary_distance_matrices(unary_moving, unary_fixed, out=None):
     return U if (nat.is_torch(unary_moving[0]) or out is not None) else U.cpu().numpy()
 
 
-def unary_distance_candidates(sc_moving, unary_fixed, k=16, col_offsets=None):
+def unary_distance_candidates(sc_moving, unary_fixed, k=16, col_offsets=None, precision="f32"):
     """Per moving nucleus the k fixed nuclei that can be cheapest, WITHOUT building a cost matrix: the Hellinger lower bound
     0.5 (sum a + sum b) - sum sqrt(a) sqrt(b) <= get_unary_distance(a, b), as a float32 GEMM on the matrix cores fused with a
     per-row top-k (K.hellinger_topk).  sc_moving: ONE of get_unary(..., 'moving')'s arrays [N, 360]; unary_fixed: the tuple (or
@@ -232,7 +232,10 @@ def unary_distance_candidates(sc_moving, unary_fixed, k=16, col_offsets=None):
     (K.hellinger_select).  lower is still returned unreduced: form the reduced value of an entry as
     lower[f, i, r] - col_offsets[f, cols[f, i, r]].  Then get_unary_distance(a_i, b_j) - col_offsets[f, j] is at least that value
     for a listed entry and at least the row's last reduced value for every column that is not listed (finite offsets up to 1e6
-    in size); a column whose offset is NaN or infinite is never listed."""
+    in size); a column whose offset is NaN or infinite is never listed.
+    precision='bf16x3': the lists come from the bf16 matrix path (K.hellinger_select(precision='bf16x3'), with or without
+    col_offsets; k <= 32) and lower = bound - K.hellinger_delta('bf16x3') (1.77e-4 against 4.31e-5): every sentence above holds,
+    but lower and the order of near-ties are not bit-compatible with the float32 lists."""
     torch = nat.torch_mod()
     a = nat.to_dev(sc_moving)
     if _stacked(unary_fixed, len(unary_fixed)) or (nat.is_torch(unary_fixed) and unary_fixed.dim() == 2) or \
@@ -240,16 +243,16 @@ def unary_distance_candidates(sc_moving, unary_fixed, k=16, col_offsets=None):
         f = nat.to_dev(unary_fixed, dev=a.device)
     else:
         f = torch.stack([nat.to_dev(x, dev=a.device) for x in unary_fixed])
-    if col_offsets is None:
+    if col_offsets is None and precision == "f32":
         cols, bound = K.hellinger_topk(a.contiguous(), f.contiguous(), k=k)
     else:
-        v = nat.to_dev(col_offsets, dev=a.device).reshape(-1)
-        cols, bound = K.hellinger_select(a.contiguous(), f.contiguous(), v=v, k=k)
-    lower = bound - K.hellinger_delta()
+        v = None if col_offsets is None else nat.to_dev(col_offsets, dev=a.device).reshape(-1)
+        cols, bound = K.hellinger_select(a.contiguous(), f.contiguous(), v=v, k=k, precision=precision)
+    lower = bound - K.hellinger_delta(precision)
     return nat.like_input(cols, sc_moving), nat.like_input(lower, sc_moving)
 
 
-def unary_distance_nearest(sc_moving, unary_fixed, k=8, candidates=32, col_offsets=None, twin=False):
+def unary_distance_nearest(sc_moving, unary_fixed, k=8, candidates=32, col_offsets=None, twin=False, precision="f32"):
     """Per moving nucleus its k nearest fixed nuclei with their EXACT distances and a proof, WITHOUT building a cost matrix:
     unary_distance_candidates' lists (the Hellinger lower bound, `candidates` columns per row) rescored exactly in one kernel
     (K.chi2_nearest).  sc_moving, unary_fixed, col_offsets: as for unary_distance_candidates; NumPy or torch in, the same kind out.
@@ -262,7 +265,10 @@ def unary_distance_nearest(sc_moving, unary_fixed, k=8, candidates=32, col_offse
     (columns with a NaN or infinite offset aside), in order, ties by column.  Entries past proven[f, i] are exact values of good
     candidates, but a column that was not listed may lie between them.  More `candidates` (up to 64) prove more: every unlisted
     column is known to cost at least the last candidate's lower bound, and a longer list moves that threshold up.
-    cols -1 with dist +inf where fewer than k columns exist; -1 with NaN and proven 0 for a moving row holding a NaN."""
+    cols -1 with dist +inf where fewer than k columns exist; -1 with NaN and proven 0 for a moving row holding a NaN.
+    precision='bf16x3': the candidates come from the bf16 matrix path (candidates <= 32) and the proof uses its error bound
+    K.hellinger_delta('bf16x3') = 1.77e-4 (float32: 4.31e-5).  dist keeps its exact bits and the guarantee its wording; proven can
+    be smaller, and the candidate bounds of the two precisions are not bit-compatible."""
     torch = nat.torch_mod()
     a = nat.to_dev(sc_moving)
     if _stacked(unary_fixed, len(unary_fixed)) or (nat.is_torch(unary_fixed) and unary_fixed.dim() == 2) or \
@@ -271,7 +277,7 @@ def unary_distance_nearest(sc_moving, unary_fixed, k=8, candidates=32, col_offse
     else:
         f = torch.stack([nat.to_dev(x, dev=a.device) for x in unary_fixed])
     v = None if col_offsets is None else nat.to_dev(col_offsets, dev=a.device).reshape(-1)
-    out = K.chi2_nearest(a.contiguous(), f.contiguous(), v=v, k=k, candidates=candidates, twin=twin)
+    out = K.chi2_nearest(a.contiguous(), f.contiguous(), v=v, k=k, candidates=candidates, twin=twin, precision=precision)
     return tuple(nat.like_input(x, sc_moving) for x in out)
 
 

@@ -13,11 +13,16 @@ Usage: python tools/hellinger_power.py [N=20000] [--rows R] [--speed] [--only-ke
                  entries per row (u = the row's 16th bound, v = 0, tau = 0; alternating, seven repetitions each), and the LIST SIZE
                  of a matrix-free pricing round: entries listed per row under the final duals of the exact mode's device solve
   --select       the priced selection (K.hellinger_select) and nothing else: its speed against hellinger_topk(k=16) at k = 16 and
-                 k = 8, with v = 0 and with v = the bound's column minima (alternating, seven repetitions each after a warm-up)
+                 k = 8, with v = 0 and with v = the bound's column minima (alternating, seven repetitions each after a warm-up);
+                 the same four legs with precision='bf16x3' (csrc/pm_hellinger_bf16.hip) alternate with them in the same process,
+                 followed by the ratio at k = 16 against three times the larger min-max spread, and the largest
+                 |bound - L_float64| of the bf16x3 lists over all rows
   --nearest      the exact rescoring (K.chi2_select_exact) and nothing else: from the same hellinger_select(k=32) lists, F = 4, k = 8,
                  the one-launch kernel against the same answer by the chain a resident-matrix selector runs (mask, gathers,
                  K.chi2_entries per pairing, scatter, price gather, argsort, gathers), with v = 0 and v = the bound's column minima
-                 (alternating, seven repetitions each after a warm-up), and the share of units with proven == k
+                 (alternating, seven repetitions each after a warm-up), and the share of units with proven == k — also from
+                 bf16x3 candidate lists under their delta (K.chi2_nearest(precision='bf16x3'))
+(--list also reports the list size at the bf16x3 delta: the same listing kernel under tau formed with cost_delta = delta_bf16x3.)
 Prints to stdout; writes nothing."""
 import argparse
 import os
@@ -67,7 +72,7 @@ def main():
         return
 
     if args.list:
-        list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed)
+        list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed, K.hellinger_delta("bf16x3"))
         return
 
     if args.select:
@@ -135,7 +140,7 @@ def main():
     print("largest |bound - L_float64| on listed entries: %.3g (delta %.3g)" % (worst, delta))
 
 
-def list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed):
+def list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed, delta_bf):
     import types
     flop = 2 * 360 * 4 * n * n
     kth = K.hellinger_topk(a, sc_f, k=16)[1][:, :, 15].contiguous()
@@ -174,6 +179,11 @@ def list_leg(torch, K, L, a, sc_m, sc_f, n, delta, timed):
         print("pairing %d (U1%d): tau = %.3g; listed under the final duals: %d entries = %.2f per row (max %s); exceeds 64 * M: %s"
               % (t, t + 1, tau, info["count"][0], info["count"][0] / n, "?" if per_row is None else int(per_row.max()),
                  "YES" if info["count"][0] > 64 * n else "no"))
+        tau = L.FilteredMatrix._tau(types.SimpleNamespace(cost_delta=delta_bf), u, v)
+        K.hellinger_list(a, sc_f[t].contiguous(), dev(u, torch.float64), dev(v, torch.float64), tau, skip=dev(col4row, torch.int32),
+                         cap=256 * n, info=info)
+        print("pairing %d (U1%d): at the bf16x3 delta %.3g, tau = %.3g: %d entries = %.2f per row; exceeds 64 * M: %s"
+              % (t, t + 1, delta_bf, tau, info["count"][0], info["count"][0] / n, "YES" if info["count"][0] > 64 * n else "no"))
 
 
 def select_leg(torch, K, a, sc_f, n, timed):
@@ -192,10 +202,12 @@ def select_leg(torch, K, a, sc_f, n, timed):
     for k in (16, 8):
         for name, v in (("v = 0", zero), ("v = column minima", vmin)):
             legs.append(("hellinger_select(k=%d, %s)" % (k, name), leg(lambda k=k, v=v: K.hellinger_select(a, sc_f, v=v, k=k))))
+            legs.append(("hellinger_select(k=%d, %s, bf16x3)" % (k, name),
+                         leg(lambda k=k, v=v: K.hellinger_select(a, sc_f, v=v, k=k, precision="bf16x3"))))
     outs = [run() for _, run in legs]                     # warm-up; and the unpriced lists are the top-k kernel's, bit for bit
     same = torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1].view(torch.int64), outs[1][1].view(torch.int64))
     print("select (k=16, v = 0) against hellinger_topk(k=16): columns and bound bits %s" % ("identical" if same else "DIFFER"))
-    moved = (outs[2][0] != outs[0][0]).any(dim=2).float().mean().item()
+    moved = (outs[3][0] != outs[0][0]).any(dim=2).float().mean().item()
     print("select rows whose list changes under v = column minima: %.1f %%" % (100.0 * moved))
     times = [[] for _ in legs]
     for _ in range(7):
@@ -204,6 +216,22 @@ def select_leg(torch, K, a, sc_f, n, timed):
     for (name, _), t in zip(legs, times):
         print("speed  %-46s median %8.2f ms  min %8.2f  max %8.2f  %6.1f TFLOP/s  (7 repetitions, alternating)"
               % (name, np.median(t), min(t), max(t), flop / np.median(t) / 1e9))
+    t32, tbf = times[1], times[2]                        # k = 16, v = 0: float32 and bf16x3
+    spread = max(max(t32) - min(t32), max(tbf) - min(tbf))
+    print("select k = 16, v = 0: float32 %.2f ms / bf16x3 %.2f ms = %.2f x; difference %.2f ms against 3 x the larger min-max spread = %.2f ms"
+          % (np.median(t32), np.median(tbf), np.median(t32) / np.median(tbf), np.median(t32) - np.median(tbf), 3 * spread))
+    delta_bf, worst, same = K.hellinger_delta("bf16x3"), 0.0, 0.0
+    cols_b, bound_b = outs[2]
+    ra, rb, ha = torch.sqrt(a), torch.sqrt(sc_f), 0.5 * a.sum(1)
+    for f in range(4):
+        hb = 0.5 * sc_f[f].sum(1)
+        for r0 in range(0, n, 2048):
+            Lref = (ha[r0:r0 + 2048, None] + hb[None, :]) - ra[r0:r0 + 2048] @ rb[f].T      # float64 on the device: the yardstick only
+            got = torch.gather(Lref, 1, cols_b[f, r0:r0 + 2048].long().clamp(min=0))
+            worst = max(worst, float((got - bound_b[f, r0:r0 + 2048]).abs().max()))
+    same = (torch.sort(cols_b, dim=2).values == torch.sort(outs[1][0], dim=2).values).all(dim=2).float().mean().item()
+    print("select bf16x3 (k=16, v = 0): largest |bound - L_float64| over all %d x 4 x 16 listed entries: %.3g (delta %.3g); rows "
+          "whose column SET equals the float32 list's: %.2f %%" % (n, worst, delta_bf, 100.0 * same))
 
 
 def nearest_leg(torch, K, a, sc_f, n, timed, candidates=32, k=8):
@@ -242,6 +270,11 @@ def nearest_leg(torch, K, a, sc_f, n, timed, candidates=32, k=8):
         full = (outs[i + 1][2] == k).float().mean().item()
         print("nearest %-20s columns and cost bits of the two routes %s; units with proven == k: %.2f %%, mean proven %.2f of %d"
               % (legs[i + 1][0][18:], "identical" if same else "DIFFER", 100.0 * full, outs[i + 1][2].float().mean().item(), k))
+    for name, v in (("v = 0", zero), ("v = column minima", vmin)):
+        for prec in ("f32", "bf16x3"):
+            pr = K.chi2_nearest(a, sc_f, v=v, k=k, candidates=candidates, precision=prec)[2]
+            print("nearest %-20s candidates from %-6s (delta %.3g): units with proven == k: %.2f %%, mean proven %.2f of %d"
+                  % (name, prec, K.hellinger_delta(prec), 100.0 * (pr == k).float().mean().item(), pr.float().mean().item(), k))
     times = [[] for _ in legs]
     for _ in range(7):
         for t, (_, run) in zip(times, legs):
