@@ -429,6 +429,43 @@ def chi2_filter_delta():
     return float(nat.load().pm_chi2_filter_delta())
 
 
+def _frames_operand(sc_b):
+    """The fixed-frames operand [M, 360] or [F, M, 360] of the Hellinger and rescoring calls, validated -> (F, M)."""
+    torch = _t()
+    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
+            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
+        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
+    _here(sc_b, "sc_b")
+    return (1 if sc_b.dim() == 2 else sc_b.shape[0]), sc_b.shape[-2]
+
+
+def _hellinger_rows(sc_a, sc_b, k, split, info, entry, kmax, k_message, priced, v=None):
+    """The body of hellinger_topk and hellinger_select.  entry(lib) -> the (size, call) pair of library functions; priced: call
+    takes the prices v (a tensor or None) after the frame count."""
+    torch = _t()
+    a = _desc(sc_a, "sc_a")
+    F, M = _frames_operand(sc_b)
+    k, split = int(k), int(split)
+    if not 1 <= k <= kmax:
+        raise ValueError(k_message)
+    if split < 0:
+        raise ValueError("split must be >= 0 (0 = automatic)")
+    N = a.shape[0]
+    if v is not None:
+        _here(_vec(v, F * M, "v"), "v")
+    size, call = entry(nat.load())
+    cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
+    bound = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
+    flag = torch.empty(1, dtype=torch.int32, device=a.device)
+    ws = nat.workspace(size(N, M, F, k), a.device)
+    prices = (ptr(v),) if priced else ()
+    check(call(ptr(a), N, ptr(sc_b), M, M * NBINS, F, *prices, k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws), ws.numel(),
+               nat.stream_ptr()))
+    if info is not None:
+        info["nonfinite"] = int(flag.item())
+    return cols, bound
+
+
 def hellinger_topk(sc_a, sc_b, k=16, split=0, info=None):
     """Per row of sc_a [N, 360] the k columns of each fixed frame sc_b [F, M, 360] (or [M, 360]: F = 1) with the smallest
     Hellinger lower bound of the chi-square cost, on the matrix cores (pm_hellinger_topk; csrc/pm_hellinger.hip) ->
@@ -436,29 +473,8 @@ def hellinger_topk(sc_a, sc_b, k=16, split=0, info=None):
     listed, -1 / NaN for a non-finite row of sc_a.  Exact cost >= bound - hellinger_delta() for listed entries, >= bound[..., -1] -
     hellinger_delta() for every other column.  split: workgroups per block of 64 rows (0 = automatic; same bits for any value).
     info (dict): receives 'nonfinite' (synchronises)."""
-    torch = _t()
-    a = _desc(sc_a, "sc_a")
-    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
-            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
-        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
-    _here(sc_b, "sc_b")
-    k, split = int(k), int(split)
-    if not 1 <= k <= 64:
-        raise ValueError("k must be 1..64")
-    if split < 0:
-        raise ValueError("split must be >= 0 (0 = automatic)")
-    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
-    N, M = a.shape[0], sc_b.shape[-2]
-    lib = nat.load()
-    cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
-    bound = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
-    flag = torch.empty(1, dtype=torch.int32, device=a.device)
-    ws = nat.workspace(lib.pm_hellinger_topk_workspace(N, M, F, k), a.device)
-    check(lib.pm_hellinger_topk(ptr(a), N, ptr(sc_b), M, M * NBINS, F, k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws), ws.numel(),
-                                nat.stream_ptr()))
-    if info is not None:
-        info["nonfinite"] = int(flag.item())
-    return cols, bound
+    return _hellinger_rows(sc_a, sc_b, k, split, info, lambda lib: (lib.pm_hellinger_topk_workspace, lib.pm_hellinger_topk),
+                           64, "k must be 1..64", priced=False)
 
 
 def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None, precision="f32"):
@@ -476,35 +492,13 @@ def hellinger_select(sc_a, sc_b, v=None, k=16, split=0, info=None, precision="f3
     sqrt-descriptors split into two bf16 pieces, three products), k <= 32 (ValueError above), panels of 256 rows.  Every sentence
     above holds with hellinger_delta('bf16x3') = 1.77e-4 in place of hellinger_delta() = 4.31e-5, EXCEPT the bit identities: the
     bounds of the two precisions are not bit-compatible (each list is valid under its own delta)."""
-    torch = _t()
     _precision(precision)
-    a = _desc(sc_a, "sc_a")
-    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
-            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
-        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
-    _here(sc_b, "sc_b")
-    k, split = int(k), int(split)
     kmax = 64 if precision == "f32" else 32
-    if not 1 <= k <= kmax:
-        raise ValueError("k must be 1..%d with precision=%r" % (kmax, precision))
-    if split < 0:
-        raise ValueError("split must be >= 0 (0 = automatic)")
-    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
-    N, M = a.shape[0], sc_b.shape[-2]
-    if v is not None:
-        _here(_vec(v, F * M, "v"), "v")
-    lib = nat.load()
-    size, call = ((lib.pm_hellinger_select_workspace, lib.pm_hellinger_select) if precision == "f32" else
-                  (lib.pm_hellinger_select_bf16_workspace, lib.pm_hellinger_select_bf16))
-    cols = torch.empty((F, N, k), dtype=torch.int32, device=a.device)
-    bound = torch.empty((F, N, k), dtype=torch.float64, device=a.device)
-    flag = torch.empty(1, dtype=torch.int32, device=a.device)
-    ws = nat.workspace(size(N, M, F, k), a.device)
-    check(call(ptr(a), N, ptr(sc_b), M, M * NBINS, F, ptr(v), k, split, ptr(cols), ptr(bound), ptr(flag), ptr(ws), ws.numel(),
-               nat.stream_ptr()))
-    if info is not None:
-        info["nonfinite"] = int(flag.item())
-    return cols, bound
+    return _hellinger_rows(
+        sc_a, sc_b, k, split, info,
+        lambda lib: ((lib.pm_hellinger_select_workspace, lib.pm_hellinger_select) if precision == "f32" else
+                     (lib.pm_hellinger_select_bf16_workspace, lib.pm_hellinger_select_bf16)),
+        kmax, "k must be 1..%d with precision=%r" % (kmax, precision), priced=True, v=v)
 
 
 def _hellinger_list_raw(a, sc_b, u, v, skip, tau, split, rc, bound, cap, count, flag):
@@ -529,12 +523,8 @@ def hellinger_list(sc_a, sc_b, u, v, tau, skip=None, cap=None, split=0, info=Non
     numbers) and 'nonfinite'.  Synchronises (the counts are read back)."""
     torch = _t()
     a = _desc(sc_a, "sc_a")
-    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
-            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
-        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
-    _here(sc_b, "sc_b")
-    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
-    N, M = a.shape[0], sc_b.shape[-2]
+    F, M = _frames_operand(sc_b)
+    N = a.shape[0]
     u, v = _vec(u, F * N, "u"), _vec(v, F * M, "v")
     _here(u, "u"), _here(v, "v")
     if skip is not None:
@@ -617,12 +607,8 @@ def chi2_select_exact(sc_a, sc_b, cand_cols, cand_bound, v=None, k=8, delta=None
     a candidate outside [-1, M), treated as absent; synchronises)."""
     torch = _t()
     a = _desc(sc_a, "sc_a")
-    if not (nat.is_torch(sc_b) and sc_b.is_cuda and sc_b.dtype == torch.float64 and sc_b.dim() in (2, 3) and sc_b.shape[-1] == NBINS
-            and sc_b.is_contiguous() and sc_b.shape[-2] >= 1 and (sc_b.dim() == 2 or 1 <= sc_b.shape[0] <= 4)):
-        raise ValueError("sc_b must be a contiguous float64 GPU tensor [M, 360] or [F, M, 360] with F = 1..4")
-    _here(sc_b, "sc_b")
-    F = 1 if sc_b.dim() == 2 else sc_b.shape[0]
-    N, M = a.shape[0], sc_b.shape[-2]
+    F, M = _frames_operand(sc_b)
+    N = a.shape[0]
     if not (nat.is_torch(cand_cols) and cand_cols.is_cuda and cand_cols.dtype == torch.int32 and cand_cols.is_contiguous()
             and cand_cols.dim() == 3 and tuple(cand_cols.shape[:2]) == (F, N) and 1 <= cand_cols.shape[2] <= 64):
         raise ValueError("cand_cols must be a contiguous int32 GPU tensor [%d, %d, kc] with kc = 1..64" % (F, N))

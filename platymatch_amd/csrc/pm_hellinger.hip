@@ -31,8 +31,11 @@
 //   per SIMD — the occupancy this kernel is built for (its 136 registers are not the limit; nothing spills).
 //   Measured (profiles/hellinger_*): 22.2 ms for 20 000 x 20 000 x 4 frames, k = 16 — a third of the float32 matrix peak.
 // Few row blocks: the fixed rows' tiles are split over S workgroups per (block, frame), each writes its sorted k-list to the
-// workspace, hl_merge_kernel merges the S lists of a row by (bound, column) (one wave per row, a k-round tournament over
-// the list heads).  Column sets are disjoint and every list is an exact top-k of its set, so the result is the same for any S.
+// workspace, hl_select_merge_kernel (without prices) merges the S lists of a row by (bound, column) (one wave per row, a k-round
+// tournament over the list heads).  Column sets are disjoint and every list is an exact top-k of its set, so the result is the
+// same for any S.
+// One ranking (hls_rank_row), one merge and one host side (pm_hellinger.h: workspace layout, split rule, argument check; here:
+// hl_prepare, hl_bands) serve every kernel of this file; pm_hellinger_bf16.hip shares the merge and the host helpers.
 //
 // Error bound.  PM_HELLINGER_DELTA bounds |L~ - L| for descriptor rows with sum a, sum b <= 1, with no assumption about the
 // MFMA's internal rounding or summation order: u = 2^-24; each input sqrt is rounded once to float32 (after a correctly
@@ -42,27 +45,18 @@
 // flushed as denormals (< 1.2e-38 each) and the float64 epilogue (3 x 2^-53) vanish in the slack of the constant below.
 #include <limits.h>
 
-#include <algorithm>
-
-#include "pm_common.h"
+#include "pm_hellinger.h"
 
 #define PM_HELLINGER_DELTA 4.31e-5
 
 namespace pm {
 
-constexpr int HL_BM = 64;                        // moving rows per workgroup = fixed rows per tile
 constexpr int HL_KC = 40;                        // bins per LDS stage
 constexpr int HL_NCH = PM_NBINS / HL_KC;         // 9 stages per tile
-constexpr int HL_TILE = PM_NBINS * HL_BM;        // floats of one 64-row block
 constexpr int HL_STAGE = HL_KC * HL_BM;          // floats of one stage (640 float4)
 constexpr int HL_CAP = 80;                       // candidate slots per row
-constexpr int HL_KMAX = 64;
 constexpr int HL_THREADS = 256;
-constexpr int HL_SMAX = 256;                     // column splits per (row block, frame)
-constexpr int HL_SPLIT_ROWS = 512 * HL_BM;       // rows x splits never exceeds this (workspace of the partial lists)
 static_assert(HL_KC % 2 == 0 && HL_NCH * HL_KC == PM_NBINS && HL_CAP >= HL_KMAX + 16 && HL_CAP <= 128, "geometry");
-
-typedef float hl_f16 __attribute__((ext_vector_type(16)));
 
 __global__ void hl_clear_flag_kernel(int32_t *flag1) { flag1[0] = 0; }
 
@@ -92,33 +86,31 @@ __global__ __launch_bounds__(256) void hl_prep_kernel(const double *__restrict__
     if (!ok && i < n) nonfinite1[0] = 1;
 }
 
-// LDS traffic between the lanes of ONE wave (its operations are processed in order; this keeps the compiler from moving them)
-__device__ __forceinline__ void hl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-struct HlEntries {      // a lane's (at most two) entries of the row being ranked
-    float dot[2];
-    int col[2];
-    double v[2];
-    int rank[2];
-    bool valid[2];
+template <int NQ>
+struct HlsEntries {      // a lane's (at most NQ) entries of the row being ranked
+    float dot[NQ];
+    int col[NQ];
+    double b[NQ], key[NQ];
+    int rank[NQ];
+    bool valid[NQ];
 };
 
-// Ranks by (bound, column) of the n <= HL_CAP buffered entries of one row, by one wave: rank = number of smaller entries
-// (columns are distinct, so the ranks are a permutation of 0..n-1).  sv: HL_CAP doubles of this wave's scratch.
-__device__ __forceinline__ void hl_rank_row(const float *cd, const int32_t *cc, int n, double ha, const double *__restrict__ hBf,
-                                            double *sv, int lane, HlEntries &e) {
+// Ranks by (key, column) of the n <= CAP buffered entries of one row, by one wave: rank = number of smaller entries (columns are
+// distinct, so the ranks are a permutation of 0..n-1).  key = bound - v[column]; vf: the frame's prices (buffered columns have
+// finite ones) or NULL: key = bound, bit for bit.  sv: CAP doubles of this wave's scratch.
+template <int CAP>
+__device__ __forceinline__ void hls_rank_row(const float *cd, const int32_t *cc, int n, double ha, const double *__restrict__ hBf,
+                                             const double *__restrict__ vf, double *sv, int lane, HlsEntries<(CAP + 63) / 64> &e) {
+    constexpr int NQ = (CAP + 63) / 64;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < NQ; ++q) {
         const int idx = lane + 64 * q;
         e.valid[q] = idx < n;
         e.dot[q] = e.valid[q] ? cd[idx] : 0.0f;
         e.col[q] = e.valid[q] ? cc[idx] : INT_MAX;
-        e.v[q] = e.valid[q] ? (ha + hBf[e.col[q]]) - (double)e.dot[q] : __builtin_inf();
-        if (idx < HL_CAP) sv[idx] = e.v[q];
+        e.b[q] = e.valid[q] ? (ha + hBf[e.col[q]]) - (double)e.dot[q] : __builtin_inf();
+        e.key[q] = e.valid[q] ? e.b[q] - (vf ? vf[e.col[q]] : 0.0) : __builtin_inf();
+        if (idx < CAP) sv[idx] = e.key[q];
         e.rank[q] = 0;
     }
     hl_wave_sync();
@@ -126,7 +118,7 @@ __device__ __forceinline__ void hl_rank_row(const float *cd, const int32_t *cc, 
         const double vj = sv[j];
         const int cj = cc[j];
 #pragma unroll
-        for (int q = 0; q < 2; ++q) e.rank[q] += (vj < e.v[q] || (vj == e.v[q] && cj < e.col[q])) ? 1 : 0;
+        for (int q = 0; q < NQ; ++q) e.rank[q] += (vj < e.key[q] || (vj == e.key[q] && cj < e.col[q])) ? 1 : 0;
     }
     hl_wave_sync();
 }
@@ -231,14 +223,14 @@ __global__ __launch_bounds__(HL_THREADS) void hl_topk_kernel(const float *__rest
                 if (tid == 0) ovf_s = 0;
                 for (int r = w; r < HL_BM; r += HL_THREADS / 64) {
                     if (__builtin_amdgcn_readfirstlane(cnt_s[r]) < HL_CAP) continue;
-                    HlEntries e;
-                    hl_rank_row(cd_s[r], cc_s[r], HL_CAP, hA_s[r], hBf, sv_s[w], lane, e);
+                    HlsEntries<2> e;
+                    hls_rank_row<HL_CAP>(cd_s[r], cc_s[r], HL_CAP, hA_s[r], hBf, nullptr, sv_s[w], lane, e);
 #pragma unroll
                     for (int q = 0; q < 2; ++q)
                         if (e.valid[q] && e.rank[q] < k) {
                             cd_s[r][e.rank[q]] = e.dot[q];
                             cc_s[r][e.rank[q]] = e.col[q];
-                            if (e.rank[q] == k - 1) tau_s[r] = e.v[q];
+                            if (e.rank[q] == k - 1) tau_s[r] = e.b[q];
                         }
                     if (lane == 0) cnt_s[r] = k;
                     hl_wave_sync();
@@ -288,110 +280,19 @@ __global__ __launch_bounds__(HL_THREADS) void hl_topk_kernel(const float *__rest
             continue;
         }
         const int n = min(__builtin_amdgcn_readfirstlane(cnt_s[r]), HL_CAP);
-        HlEntries e;
-        hl_rank_row(cd_s[r], cc_s[r], n, ha, hBf, sv_s[w], lane, e);
+        HlsEntries<2> e;
+        hls_rank_row<HL_CAP>(cd_s[r], cc_s[r], n, ha, hBf, nullptr, sv_s[w], lane, e);
 #pragma unroll
         for (int q = 0; q < 2; ++q)
             if (e.valid[q] && e.rank[q] < k) {
                 out_col[base + e.rank[q]] = e.col[q];
-                out_val[base + e.rank[q]] = e.v[q];
+                out_val[base + e.rank[q]] = e.b[q];
             }
         for (int t = min(n, k) + lane; t < k; t += 64) {
             out_col[base + t] = -1;
             out_val[base + t] = inf;
         }
     }
-}
-
-// The S sorted partial lists of one (frame, row) -> its k smallest by (bound, column).  One wave per row: a lane holds the
-// heads of lists lane, lane + 64, .. (S <= 256); k rounds of a wave-wide minimum, the winning list steps forward.
-__global__ __launch_bounds__(256) void hl_merge_kernel(const int32_t *__restrict__ pcol, const double *__restrict__ pval,
-                                                       const double *__restrict__ hA, int nA, int S, int k,
-                                                       int32_t *__restrict__ out_col, double *__restrict__ out_val) {
-    const int lane = threadIdx.x & 63, f = blockIdx.y;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= nA) return;
-    const size_t base = ((size_t)f * nA + row) * S * k, obase = ((size_t)f * nA + row) * k;
-    const double inf = __builtin_inf(), ha = hA[row];
-    if (ha != ha) {
-        for (int t = lane; t < k; t += 64) {
-            out_col[obase + t] = -1;
-            out_val[obase + t] = ha;
-        }
-        return;
-    }
-    int pos[4], hc[4];
-    double hv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int l = lane + 64 * q;
-        pos[q] = 0;
-        hc[q] = l < S ? pcol[base + (size_t)l * k] : -1;
-        hv[q] = hc[q] >= 0 ? pval[base + (size_t)l * k] : inf;
-        if (hc[q] < 0) hc[q] = INT_MAX;
-    }
-    for (int t = 0; t < k; ++t) {
-        double bv = hv[0];
-        int bc = hc[0];
-#pragma unroll
-        for (int q = 1; q < 4; ++q)
-            if (hv[q] < bv || (hv[q] == bv && hc[q] < bc)) {
-                bv = hv[q];
-                bc = hc[q];
-            }
-        double mv = bv;
-        int mc = bc;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(mv, off, PM_WAVE);
-            const int oc = __shfl_xor(mc, off, PM_WAVE);
-            if (ov < mv || (ov == mv && oc < mc)) {
-                mv = ov;
-                mc = oc;
-            }
-        }
-        if (lane == 0) {
-            out_col[obase + t] = mc == INT_MAX ? -1 : mc;
-            out_val[obase + t] = mc == INT_MAX ? inf : mv;
-        }
-        if (mc == INT_MAX) continue;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (hc[q] == mc) {          // (columns are distinct: exactly one head of one lane)
-                const int l = lane + 64 * q;
-                ++pos[q];
-                hc[q] = pos[q] < k ? pcol[base + (size_t)l * k + pos[q]] : -1;
-                hv[q] = hc[q] >= 0 ? pval[base + (size_t)l * k + pos[q]] : inf;
-                if (hc[q] < 0) hc[q] = INT_MAX;
-            }
-    }
-}
-
-struct HlWorkspace {
-    size_t rA, rB, hA, hB, pcol, pval, bytes;      // byte offsets
-};
-
-static HlWorkspace hl_workspace(int nA, int nB, int F, int k) {
-    const size_t RB = ((size_t)nA + HL_BM - 1) / HL_BM, CT = ((size_t)nB + HL_BM - 1) / HL_BM;
-    const size_t P = std::min(RB * HL_BM * HL_SMAX, (size_t)HL_SPLIT_ROWS);      // rows x splits of the partial lists, per frame
-    HlWorkspace w;
-    size_t o = 0;
-    w.rA = o, o += align_up(RB * HL_TILE * sizeof(float), 256);
-    w.rB = o, o += align_up((size_t)F * CT * HL_TILE * sizeof(float), 256);
-    w.hA = o, o += align_up(RB * HL_BM * sizeof(double), 256);
-    w.hB = o, o += align_up((size_t)F * CT * HL_BM * sizeof(double), 256);
-    w.pcol = o, o += align_up((size_t)F * P * k * sizeof(int32_t), 256);
-    w.pval = o, o += align_up((size_t)F * P * k * sizeof(double), 256);
-    w.bytes = o;
-    return w;
-}
-
-// column splits per (row block, frame): the caller's, or enough workgroups for two per CU of a 256-CU device; never more than
-// there are tiles, than HL_SMAX, or than the partial lists' workspace holds
-static int hl_splits(int split, long RB, long CT, int F) {
-    const long cap = std::min({CT, (long)HL_SMAX, std::max(1L, (long)(HL_SPLIT_ROWS / HL_BM) / RB)});
-    const long want = split > 0 ? split : (512 + RB * F - 1) / (RB * F);
-    return (int)std::max(1L, std::min(want, cap));
 }
 
 // ---- threshold listing: every entry whose bound, reduced by the duals, is at most tau ---------------------------------------
@@ -581,23 +482,6 @@ __global__ __launch_bounds__(HL_THREADS, 2) void hl_list_kernel(const float *__r
     }
 }
 
-struct HlListWorkspace {
-    size_t rA, rB, hA, hB, cnt, bytes;      // byte offsets
-};
-
-static HlListWorkspace hl_list_workspace(int nA, int nB, int F) {
-    const size_t PB = ((size_t)nA + HLL_BM - 1) / HLL_BM, CT = ((size_t)nB + HLL_BM - 1) / HLL_BM;
-    HlListWorkspace w;
-    size_t o = 0;
-    w.rA = o, o += align_up(PB * 2 * HL_TILE * sizeof(float), 256);
-    w.rB = o, o += align_up((size_t)F * CT * 2 * HL_TILE * sizeof(float), 256);
-    w.hA = o, o += align_up(PB * HLL_BM * sizeof(double), 256);
-    w.hB = o, o += align_up((size_t)F * CT * HLL_BM * sizeof(double), 256);
-    w.cnt = o, o += 256;
-    w.bytes = o;
-    return w;
-}
-
 // ---- priced selection: per row the k entries of smallest bound reduced by the column prices ---------------------------------
 // hl_select_kernel answers the solver's row_select(v, k): per (frame, moving row) the k columns of smallest
 //     key = L~ - v[f][j]   (float64, in that order),   L~ = (hA_i + hB_j) - (double)dot — the bits of the two kernels above,
@@ -621,45 +505,6 @@ static HlListWorkspace hl_list_workspace(int nA, int nB, int F) {
 // Column tiles are split over S workgroups per (panel, frame); each writes its sorted partial list of (column, bound) and
 // hl_select_merge_kernel re-forms the keys and merges by (key, column): disjoint column sets, exact partial lists, the same
 // subtraction — the result does not depend on S.
-constexpr int HLS_SPLIT_ROWS = 512 * HLL_BM;      // rows x splits never exceeds this (workspace of the partial lists)
-constexpr double HLS_TAU0 = 1.7976931348623157e308;
-
-template <int NQ>
-struct HlsEntries {      // a lane's (at most NQ) entries of the row being ranked
-    float dot[NQ];
-    int col[NQ];
-    double b[NQ], key[NQ];
-    int rank[NQ];
-    bool valid[NQ];
-};
-
-// hl_rank_row for keys: ranks by (key, column) of the n <= CAP buffered entries of one row, by one wave.  sv: CAP doubles of this
-// wave's scratch; vf: the frame's prices or NULL (buffered columns have finite prices).
-template <int CAP>
-__device__ __forceinline__ void hls_rank_row(const float *cd, const int32_t *cc, int n, double ha, const double *__restrict__ hBf,
-                                             const double *__restrict__ vf, double *sv, int lane, HlsEntries<(CAP + 63) / 64> &e) {
-    constexpr int NQ = (CAP + 63) / 64;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int idx = lane + 64 * q;
-        e.valid[q] = idx < n;
-        e.dot[q] = e.valid[q] ? cd[idx] : 0.0f;
-        e.col[q] = e.valid[q] ? cc[idx] : INT_MAX;
-        e.b[q] = e.valid[q] ? (ha + hBf[e.col[q]]) - (double)e.dot[q] : __builtin_inf();
-        e.key[q] = e.valid[q] ? e.b[q] - (vf ? vf[e.col[q]] : 0.0) : __builtin_inf();
-        if (idx < CAP) sv[idx] = e.key[q];
-        e.rank[q] = 0;
-    }
-    hl_wave_sync();
-    for (int j = 0; j < n; ++j) {
-        const double vj = sv[j];
-        const int cj = cc[j];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) e.rank[q] += (vj < e.key[q] || (vj == e.key[q] && cj < e.col[q])) ? 1 : 0;
-    }
-    hl_wave_sync();
-}
-
 // out_col / out_val: the final arrays [F][nA][k] when S == 1, the partial lists [F][nA][S][k] otherwise.
 template <int CAP>
 __global__ __launch_bounds__(HL_THREADS, 2) void hl_select_kernel(const float *__restrict__ rAt, const float *__restrict__ rBt,
@@ -686,12 +531,13 @@ __global__ __launch_bounds__(HL_THREADS, 2) void hl_select_kernel(const float *_
 
     if (tid < HLL_BM) {
         hA_s[tid] = hA[(size_t)pb * HLL_BM + tid];                                      // (padded: NaN past the cloud's end)
-        tau_s[tid] = HLS_TAU0;
+        tau_s[tid] = HL_TAU0;
         cnt_s[tid] = 0;
     }
     if (tid == 0) ovf_s = 0;
 
-    // the stage copies and operand offsets of hl_list_kernel
+    // the stage copies, operand offsets and stage loop of hl_list_kernel, written out: moved with that kernel's into one inlined
+    // template that calls the epilogue, this kernel compiled to 235 (CAP = 32) and 300 (CAP = 80) registers against 196 and 256
     int so[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
@@ -853,7 +699,7 @@ __global__ __launch_bounds__(HL_THREADS, 2) void hl_select_kernel(const float *_
     }
 }
 
-// hl_merge_kernel for keys: the S sorted partial lists (column, bound) of one (frame, row) -> its k smallest by (key, column),
+// The merge of all three row-list kernels (here and pm_hellinger_bf16.hip): the S sorted partial lists (column, bound) of one (frame, row) -> its k smallest by (key, column),
 // key = bound - v[column] re-formed by the subtraction hl_select_kernel ranked with.  One wave per row; the lane that holds the
 // winning head writes it.
 __global__ __launch_bounds__(256) void hl_select_merge_kernel(const int32_t *__restrict__ pcol, const double *__restrict__ pval,
@@ -925,126 +771,101 @@ __global__ __launch_bounds__(256) void hl_select_merge_kernel(const int32_t *__r
     }
 }
 
-struct HlSelectWorkspace {
-    size_t rA, rB, hA, hB, pcol, pval, bytes;      // byte offsets
+// ---- host side: the three entry points' geometries (pm_hellinger.h), what they run first, and their launches in bands --------
+// automatic splits: two workgroups per CU of a 256-CU device for the resident kernel; four such rounds for the selection (a split
+// repeats the first tiles' cuts and adds a merge, but a last round that is a quarter full costs more); eight rounds of three per
+// CU for the listing (a split costs nothing there — no partial lists, no merge — and short workgroups keep the last round full)
+constexpr HlGeometry HL_TOPK = {HL_BM, HL_BM, HL_TILE * sizeof(float), true, HL_KMAX, 512};
+constexpr HlGeometry HL_SELECT = {HLL_BM, HLL_BM, HL_TILE * sizeof(float), true, HL_KMAX, 2048};
+constexpr HlGeometry HL_LIST = {HLL_BM, HLL_BM, HL_TILE * sizeof(float), false, 0, 6144};
+
+struct HlBuffers {
+    float *rA, *rB;
+    double *hA, *hB, *pval;
+    int32_t *pcol;
+    unsigned long long *cnt;
 };
 
-static HlSelectWorkspace hl_select_workspace(int nA, int nB, int F, int k) {
-    const size_t PB = ((size_t)nA + HLL_BM - 1) / HLL_BM, CT = ((size_t)nB + HLL_BM - 1) / HLL_BM;
-    const size_t P = std::min(PB * HLL_BM * HL_SMAX, (size_t)HLS_SPLIT_ROWS);      // rows x splits of the partial lists, per frame
-    HlSelectWorkspace w;
-    size_t o = 0;
-    w.rA = o, o += align_up(PB * 2 * HL_TILE * sizeof(float), 256);
-    w.rB = o, o += align_up((size_t)F * CT * 2 * HL_TILE * sizeof(float), 256);
-    w.hA = o, o += align_up(PB * HLL_BM * sizeof(double), 256);
-    w.hB = o, o += align_up((size_t)F * CT * HLL_BM * sizeof(double), 256);
-    w.pcol = o, o += align_up((size_t)F * P * k * sizeof(int32_t), 256);
-    w.pval = o, o += align_up((size_t)F * P * k * sizeof(double), 256);
-    w.bytes = o;
-    return w;
+// clears the flag (and the listing's counters), then the sqrt-descriptors and half row sums of both clouds into the workspace
+static HlBuffers hl_prepare(const HlGeometry &g, const HlLayout &L, void *ws, const double *scA, int nA, const double *scB, int nB,
+                            size_t frame_stride, int F, int32_t *nonfinite1, hipStream_t s) {
+    char *base = (char *)ws;
+    const HlBuffers b = {(float *)(base + L.rA),    (float *)(base + L.rB),     (double *)(base + L.hA),           (double *)(base + L.hB),
+                         (double *)(base + L.pval), (int32_t *)(base + L.pcol), (unsigned long long *)(base + L.cnt)};
+    const int padA = (int)(L.PB * g.block_rows), padB = (int)(L.CT * g.tile_rows);
+    if (g.lists)
+        hl_clear_flag_kernel<<<1, 1, 0, s>>>(nonfinite1);
+    else
+        hl_list_clear_kernel<<<1, 64, 0, s>>>(b.cnt, F, nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((padA + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, padA, b.rA, b.hA, __builtin_nan(""), nonfinite1);
+    hl_prep_kernel<<<dim3((unsigned int)((padB + 255) / 256), F), 256, 0, s>>>(scB, frame_stride, nB, padB, b.rB, b.hB, __builtin_inf(),
+                                                                              nonfinite1);
+    return b;
 }
 
-// hl_splits for panels: the caller's, or enough workgroups for four rounds of two per CU of a 256-CU device (a split repeats the
-// first tiles' cuts and adds a merge, but a last round that is a quarter full costs more); never more than there are tiles,
-// than HL_SMAX, or than the partial lists' workspace holds
-static int hl_select_splits(int split, long PB, long CT, int F) {
-    const long cap = std::min({CT, (long)HL_SMAX, std::max(1L, (long)(HLS_SPLIT_ROWS / HLL_BM) / PB)});
-    const long want = split > 0 ? split : (2048 + PB * F - 1) / (PB * F);
-    return (int)std::max(1L, std::min(want, cap));
+// launch(first block, grid) per band of row blocks: one launch stays under 2^32 work-items, as pm_chi2.hip's launchers cut theirs
+template <class Launch>
+static void hl_bands(long blocks, int S, int F, Launch launch) {
+    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * F));
+    for (long b0 = 0; b0 < blocks; b0 += band) launch((int)b0, dim3((unsigned int)(std::min(band, blocks - b0) * S), F));
 }
 
 }  // namespace pm
 
-extern "C" size_t pm_hellinger_list_workspace(int nA, int nB, int n_frames) {
-    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4) return 0;
-    return pm::hl_list_workspace(nA, nB, n_frames).bytes;
-}
+extern "C" size_t pm_hellinger_list_workspace(int nA, int nB, int n_frames) { return pm::hl_layout(pm::HL_LIST, nA, nB, n_frames, 0).bytes; }
 
 extern "C" int pm_hellinger_list(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames,
                                  const double *u, const double *v, const int32_t *skip, double tau, int split, int32_t *out_rc,
                                  double *out_bound, int cap, int32_t *count, int32_t *nonfinite1, void *ws, size_t ws_bytes,
                                  void *stream) {
     using namespace pm;
-    if (!scA || !scB || !u || !v || !out_rc || !out_bound || !count || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 ||
-        n_frames > 4 || cap <= 0 || split < 0 || tau != tau || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
-        return PM_ERR_INVALID_ARG;
-    const HlListWorkspace L = hl_list_workspace(nA, nB, n_frames);
-    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    const HlLayout L = hl_layout(HL_LIST, nA, nB, n_frames, 0);
+    const bool args = scA && scB && u && v && out_rc && out_bound && count && nonfinite1 && cap > 0 && tau == tau;
+    if (const int err = hl_check(args, L, nB, n_frames, split, frame_stride, ws, ws_bytes)) return err;
     hipStream_t s = (hipStream_t)stream;
-    char *base = (char *)ws;
-    float *rA = (float *)(base + L.rA), *rB = (float *)(base + L.rB);
-    double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
-    unsigned long long *cnt = (unsigned long long *)(base + L.cnt);
-    const long PB = ((long)nA + HLL_BM - 1) / HLL_BM, CT = ((long)nB + HLL_BM - 1) / HLL_BM;
-    // workgroups the column tiles of a (panel, frame) are divided over: the caller's, or enough for eight rounds of three per CU
-    // of a 256-CU device (a split costs nothing here — no partial lists, no merge — and short workgroups keep the last round full)
-    const long want = split > 0 ? split : (6144 + PB * n_frames - 1) / (PB * n_frames);
-    const int S = (int)std::max(1L, std::min({want, CT, (long)HL_SMAX}));
+    const int S = hl_splits(HL_LIST, L, split, n_frames), CT = (int)L.CT;
     // a +inf bound (a padding or non-finite fixed row) fails the comparison against any finite tau: tau = +inf becomes the largest one
-    const double tau_f = std::min(tau, 1.7976931348623157e308);
+    const double tau_f = std::min(tau, HL_TAU0);
 
-    hl_list_clear_kernel<<<1, 64, 0, s>>>(cnt, n_frames, nonfinite1);
-    hl_prep_kernel<<<dim3((unsigned int)((PB * HLL_BM + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, (int)(PB * HLL_BM), rA, hA,
-                                                                                     __builtin_nan(""), nonfinite1);
-    hl_prep_kernel<<<dim3((unsigned int)((CT * HLL_BM + 255) / 256), n_frames), 256, 0, s>>>(scB, frame_stride, nB, (int)(CT * HLL_BM),
-                                                                                            rB, hB, __builtin_inf(), nonfinite1);
-    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * n_frames));      // under 2^32 work-items per launch
-    for (long b0 = 0; b0 < PB; b0 += band) {
-        const long nb = std::min(band, PB - b0);
-        hl_list_kernel<<<dim3((unsigned int)(nb * S), n_frames), HL_THREADS, 0, s>>>(rA, rB, hA, hB, u, v, skip, tau_f, nA, nB, (int)CT,
-                                                                                    (int)b0, S, cap, out_rc, out_bound, cnt);
-    }
-    hl_list_finish_kernel<<<1, 64, 0, s>>>(cnt, n_frames, count);
+    const HlBuffers b = hl_prepare(HL_LIST, L, ws, scA, nA, scB, nB, frame_stride, n_frames, nonfinite1, s);
+    hl_bands(L.PB, S, n_frames, [&](int b0, dim3 grid) {
+        hl_list_kernel<<<grid, HL_THREADS, 0, s>>>(b.rA, b.rB, b.hA, b.hB, u, v, skip, tau_f, nA, nB, CT, b0, S, cap, out_rc, out_bound, b.cnt);
+    });
+    hl_list_finish_kernel<<<1, 64, 0, s>>>(b.cnt, n_frames, count);
     return launch_status();
 }
 
 extern "C" size_t pm_hellinger_select_workspace(int nA, int nB, int n_frames, int k) {
-    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 || k > pm::HL_KMAX) return 0;
-    return pm::hl_select_workspace(nA, nB, n_frames, k).bytes;
+    return pm::hl_layout(pm::HL_SELECT, nA, nB, n_frames, k).bytes;
 }
 
 extern "C" int pm_hellinger_select(const double *scA, int nA, const double *scB, int nB, size_t frame_stride, int n_frames,
                                    const double *v, int k, int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1,
                                    void *ws, size_t ws_bytes, void *stream) {
     using namespace pm;
-    if (!scA || !scB || !out_col || !out_bound || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 ||
-        k > HL_KMAX || split < 0 || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
-        return PM_ERR_INVALID_ARG;
-    const HlSelectWorkspace L = hl_select_workspace(nA, nB, n_frames, k);
-    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    const HlLayout L = hl_layout(HL_SELECT, nA, nB, n_frames, k);
+    const bool args = scA && scB && out_col && out_bound && nonfinite1;
+    if (const int err = hl_check(args, L, nB, n_frames, split, frame_stride, ws, ws_bytes)) return err;
     hipStream_t s = (hipStream_t)stream;
-    char *base = (char *)ws;
-    float *rA = (float *)(base + L.rA), *rB = (float *)(base + L.rB);
-    double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
-    int32_t *pcol = (int32_t *)(base + L.pcol);
-    double *pval = (double *)(base + L.pval);
-    const long PB = ((long)nA + HLL_BM - 1) / HLL_BM, CT = ((long)nB + HLL_BM - 1) / HLL_BM;
-    const int S = hl_select_splits(split, PB, CT, n_frames);
-    int32_t *oc = S == 1 ? out_col : pcol;
-    double *ov = S == 1 ? out_bound : pval;
+    const int S = hl_splits(HL_SELECT, L, split, n_frames), CT = (int)L.CT;
 
-    hl_clear_flag_kernel<<<1, 1, 0, s>>>(nonfinite1);
-    hl_prep_kernel<<<dim3((unsigned int)((PB * HLL_BM + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, (int)(PB * HLL_BM), rA, hA,
-                                                                                     __builtin_nan(""), nonfinite1);
-    hl_prep_kernel<<<dim3((unsigned int)((CT * HLL_BM + 255) / 256), n_frames), 256, 0, s>>>(scB, frame_stride, nB, (int)(CT * HLL_BM),
-                                                                                            rB, hB, __builtin_inf(), nonfinite1);
-    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * n_frames));      // under 2^32 work-items per launch
-    for (long b0 = 0; b0 < PB; b0 += band) {
-        const dim3 grid((unsigned int)(std::min(band, PB - b0) * S), n_frames);
+    const HlBuffers b = hl_prepare(HL_SELECT, L, ws, scA, nA, scB, nB, frame_stride, n_frames, nonfinite1, s);
+    int32_t *oc = S == 1 ? out_col : b.pcol;
+    double *ov = S == 1 ? out_bound : b.pval;
+    hl_bands(L.PB, S, n_frames, [&](int b0, dim3 grid) {
         if (k <= 16)
-            hl_select_kernel<32><<<grid, HL_THREADS, 0, s>>>(rA, rB, hA, hB, v, nA, nB, (int)CT, (int)b0, S, k, oc, ov);
+            hl_select_kernel<32><<<grid, HL_THREADS, 0, s>>>(b.rA, b.rB, b.hA, b.hB, v, nA, nB, CT, b0, S, k, oc, ov);
         else
-            hl_select_kernel<HL_CAP><<<grid, HL_THREADS, 0, s>>>(rA, rB, hA, hB, v, nA, nB, (int)CT, (int)b0, S, k, oc, ov);
-    }
+            hl_select_kernel<HL_CAP><<<grid, HL_THREADS, 0, s>>>(b.rA, b.rB, b.hA, b.hB, v, nA, nB, CT, b0, S, k, oc, ov);
+    });
     if (S > 1)
-        hl_select_merge_kernel<<<dim3((unsigned int)((nA + 3) / 4), n_frames), 256, 0, s>>>(pcol, pval, hA, v, nA, nB, S, k, out_col,
+        hl_select_merge_kernel<<<dim3((unsigned int)((nA + 3) / 4), n_frames), 256, 0, s>>>(b.pcol, b.pval, b.hA, v, nA, nB, S, k, out_col,
                                                                                            out_bound);
     return launch_status();
 }
 
 extern "C" size_t pm_hellinger_topk_workspace(int nA, int nB, int n_frames, int k) {
-    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 || k > pm::HL_KMAX) return 0;
-    return pm::hl_workspace(nA, nB, n_frames, k).bytes;
+    return pm::hl_layout(pm::HL_TOPK, nA, nB, n_frames, k).bytes;
 }
 
 extern "C" int pm_hellinger_delta(double *delta1_host) {
@@ -1057,33 +878,19 @@ extern "C" int pm_hellinger_topk(const double *scA, int nA, const double *scB, i
                                  int split, int32_t *out_col, double *out_bound, int32_t *nonfinite1, void *ws, size_t ws_bytes,
                                  void *stream) {
     using namespace pm;
-    if (!scA || !scB || !out_col || !out_bound || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 ||
-        k > HL_KMAX || split < 0 || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
-        return PM_ERR_INVALID_ARG;
-    const HlWorkspace L = hl_workspace(nA, nB, n_frames, k);
-    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    const HlLayout L = hl_layout(HL_TOPK, nA, nB, n_frames, k);
+    const bool args = scA && scB && out_col && out_bound && nonfinite1;
+    if (const int err = hl_check(args, L, nB, n_frames, split, frame_stride, ws, ws_bytes)) return err;
     hipStream_t s = (hipStream_t)stream;
-    char *base = (char *)ws;
-    float *rA = (float *)(base + L.rA), *rB = (float *)(base + L.rB);
-    double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
-    int32_t *pcol = (int32_t *)(base + L.pcol);
-    double *pval = (double *)(base + L.pval);
-    const long RB = ((long)nA + HL_BM - 1) / HL_BM, CT = ((long)nB + HL_BM - 1) / HL_BM;
-    const int S = hl_splits(split, RB, CT, n_frames);
+    const int S = hl_splits(HL_TOPK, L, split, n_frames), CT = (int)L.CT;
 
-    hl_clear_flag_kernel<<<1, 1, 0, s>>>(nonfinite1);
-    hl_prep_kernel<<<dim3((unsigned int)((RB * HL_BM + 255) / 256), 1), 256, 0, s>>>(scA, 0, nA, (int)(RB * HL_BM), rA, hA,
-                                                                                    __builtin_nan(""), nonfinite1);
-    hl_prep_kernel<<<dim3((unsigned int)((CT * HL_BM + 255) / 256), n_frames), 256, 0, s>>>(scB, frame_stride, nB, (int)(CT * HL_BM), rB,
-                                                                                           hB, __builtin_inf(), nonfinite1);
-    // one launch stays under 2^32 work-items: bands of row blocks, as pm_chi2.hip's launchers cut theirs
-    const long band = std::max(1L, (0xffffffffL / HL_THREADS) / ((long)S * n_frames));
-    for (long b0 = 0; b0 < RB; b0 += band) {
-        const long nb = std::min(band, RB - b0);
-        hl_topk_kernel<<<dim3((unsigned int)(nb * S), n_frames), HL_THREADS, 0, s>>>(rA, rB, hA, hB, nA, (int)CT, (int)b0, S, k,
-                                                                                    S == 1 ? out_col : pcol, S == 1 ? out_bound : pval);
-    }
-    if (S > 1)
-        hl_merge_kernel<<<dim3((unsigned int)((nA + 3) / 4), n_frames), 256, 0, s>>>(pcol, pval, hA, nA, S, k, out_col, out_bound);
+    const HlBuffers b = hl_prepare(HL_TOPK, L, ws, scA, nA, scB, nB, frame_stride, n_frames, nonfinite1, s);
+    hl_bands(L.PB, S, n_frames, [&](int b0, dim3 grid) {
+        hl_topk_kernel<<<grid, HL_THREADS, 0, s>>>(b.rA, b.rB, b.hA, b.hB, nA, CT, b0, S, k, S == 1 ? out_col : b.pcol,
+                                                   S == 1 ? out_bound : b.pval);
+    });
+    if (S > 1)      // (no prices: the keys are the bounds, nB is not read)
+        hl_select_merge_kernel<<<dim3((unsigned int)((nA + 3) / 4), n_frames), 256, 0, s>>>(b.pcol, b.pval, b.hA, nullptr, nA, nB, S, k,
+                                                                                           out_col, out_bound);
     return launch_status();
 }

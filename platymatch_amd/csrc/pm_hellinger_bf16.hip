@@ -67,22 +67,13 @@
 // this delta in place of pm_hellinger_delta.
 #include <limits.h>
 
-#include <algorithm>
-
-#include "pm_common.h"
+#include "pm_hellinger.h"
 
 #define PM_HELLINGER_DELTA_BF16X3 1.77e-4
 
 namespace pm {
 
-// pm_hellinger.hip's kernels that serve here unchanged
-__global__ void hl_clear_flag_kernel(int32_t *flag1);
-__global__ __launch_bounds__(256) void hl_select_merge_kernel(const int32_t *__restrict__ pcol, const double *__restrict__ pval,
-                                                              const double *__restrict__ hA, const double *__restrict__ v, int nA,
-                                                              int nB, int S, int k, int32_t *__restrict__ out_col,
-                                                              double *__restrict__ out_val);
-
-constexpr int HLB_BLK = 64;                            // rows per block of the layout
+constexpr int HLB_BLK = HL_BM;                         // rows per block of the layout
 constexpr int HLB_STEPS = 24;                          // 16-bin steps per tile (384 bins, 360 of them real)
 constexpr int HLB_GROUPS = 2 * HLB_STEPS;              // 8-bin groups
 constexpr int HLB_BLK_U4 = HLB_GROUPS * 2 * HLB_BLK;   // 16-byte pieces of a block (6 144)
@@ -91,15 +82,11 @@ constexpr int HLB_PM = 256;                            // moving rows per panel
 constexpr int HLB_TN = 128;                            // fixed rows per tile
 constexpr int HLB_THREADS = 512;
 constexpr int HLB_KMAX = 32;
-constexpr int HLB_SMAX = 256;                          // column splits per (panel, frame): what hl_select_merge_kernel merges
-constexpr int HLB_SPLIT_ROWS = 512 * HLB_PM;           // rows x splits never exceeds this (workspace of the partial lists)
 constexpr int HLB_XP = 4, HLB_XR = 8;                  // panels x column ranges of the group an XCD holds at a time
-constexpr double HLB_TAU0 = 1.7976931348623157e308;
 static_assert(16 * HLB_STEPS >= PM_NBINS && HLB_PM == 4 * HLB_BLK && HLB_TN == 2 * HLB_BLK && HLB_THREADS == 2 * HLB_STEP_U4 &&
                   HLB_XP * HLB_XR == 32,
               "geometry");
 
-typedef float hlb_f16 __attribute__((ext_vector_type(16)));
 typedef __bf16 hlb_bf8 __attribute__((ext_vector_type(8)));
 typedef unsigned int hlb_u4 __attribute__((ext_vector_type(4)));      // a 16-byte piece in registers and LDS
 
@@ -155,13 +142,6 @@ __global__ __launch_bounds__(256) void hlb_prep_kernel(const double *__restrict_
     if (!ok && i < n) nonfinite1[0] = 1;
 }
 
-// LDS traffic between the lanes of ONE wave (its operations are processed in order; this keeps the compiler from moving them)
-__device__ __forceinline__ void hlb_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // the float32 pre-test's two sides (header): s below hB - v, t above tau - hA, each by 2^-21 of its operands' magnitudes
 __device__ __forceinline__ float hlb_below(double hb, double v) {
     if (hb == __builtin_inf()) return __builtin_inff();
@@ -192,13 +172,13 @@ __device__ __forceinline__ void hlb_rank_row(const float *cd, const int32_t *cc,
     e.key = e.valid ? e.b - (vf ? vf[e.col] : 0.0) : __builtin_inf();
     if (lane < CAP) sv[lane] = e.key;
     e.rank = 0;
-    hlb_wave_sync();
+    hl_wave_sync();
     for (int j = 0; j < n; ++j) {
         const double vj = sv[j];
         const int cj = cc[j];
         e.rank += (vj < e.key || (vj == e.key && cj < e.col)) ? 1 : 0;
     }
-    hlb_wave_sync();
+    hl_wave_sync();
 }
 
 // R = S * F column ranges (frame f = range / S, split sp = range % S), PBn panels from pb0 on; per: work items per XCD.
@@ -239,8 +219,8 @@ __global__ __launch_bounds__(HLB_THREADS) void hl_select_bf16_kernel(const uint4
     if (tid < HLB_PM) {
         const double ha = hA[(size_t)pb * HLB_PM + tid];                                // (padded: NaN past the cloud's end)
         hA_s[tid] = ha;
-        tau_s[tid] = HLB_TAU0;
-        tr_s[tid] = hlb_above(HLB_TAU0, ha);
+        tau_s[tid] = HL_TAU0;
+        tr_s[tid] = hlb_above(HL_TAU0, ha);
         cnt_s[tid] = 0;
     }
     if (tid == 0) ovf_s = 0;
@@ -257,7 +237,7 @@ __global__ __launch_bounds__(HLB_THREADS) void hl_select_bf16_kernel(const uint4
     B_s[0][tid] = pbr;
     __syncthreads();
 
-    hlb_f16 acc00, acc01, acc10, acc11;              // (row half, column half) of the wave's 64 x 64
+    hl_f16 acc00, acc01, acc10, acc11;              // (row half, column half) of the wave's 64 x 64
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc00[e] = acc01[e] = acc10[e] = acc11[e] = 0.0f;
     for (int tile = t0; tile < t1; ++tile) {
@@ -357,7 +337,7 @@ __global__ __launch_bounds__(HLB_THREADS) void hl_select_bf16_kernel(const uint4
                         }
                     }
                     if (lane == 0) cnt_s[r] = k;
-                    hlb_wave_sync();
+                    hl_wave_sync();
                 }
                 __syncthreads();
             }
@@ -393,38 +373,13 @@ __global__ __launch_bounds__(HLB_THREADS) void hl_select_bf16_kernel(const uint4
     }
 }
 
-struct HlbWorkspace {
-    size_t rA, rB, hA, hB, pcol, pval, bytes;      // byte offsets
-};
-
-static HlbWorkspace hlb_workspace(int nA, int nB, int F, int k) {
-    const size_t PB = ((size_t)nA + HLB_PM - 1) / HLB_PM, CT = ((size_t)nB + HLB_TN - 1) / HLB_TN;
-    const size_t P = std::min(PB * HLB_PM * HLB_SMAX, (size_t)HLB_SPLIT_ROWS);      // rows x splits of the partial lists, per frame
-    HlbWorkspace w;
-    size_t o = 0;
-    w.rA = o, o += align_up(PB * 4 * HLB_BLK_U4 * sizeof(uint4), 256);
-    w.rB = o, o += align_up((size_t)F * CT * 2 * HLB_BLK_U4 * sizeof(uint4), 256);
-    w.hA = o, o += align_up(PB * HLB_PM * sizeof(double), 256);
-    w.hB = o, o += align_up((size_t)F * CT * HLB_TN * sizeof(double), 256);
-    w.pcol = o, o += align_up((size_t)F * P * k * sizeof(int32_t), 256);
-    w.pval = o, o += align_up((size_t)F * P * k * sizeof(double), 256);
-    w.bytes = o;
-    return w;
-}
-
-// column splits per (panel, frame): the caller's, or enough workgroups for four rounds of one per CU of a 256-CU device; never
-// more than there are tiles, than HLB_SMAX, or than the partial lists' workspace holds
-static int hlb_splits(int split, long PB, long CT, int F) {
-    const long cap = std::min({CT, (long)HLB_SMAX, std::max(1L, (long)(HLB_SPLIT_ROWS / HLB_PM) / PB)});
-    const long want = split > 0 ? split : (1024 + PB * F - 1) / (PB * F);
-    return (int)std::max(1L, std::min(want, cap));
-}
+// automatic splits: four rounds of one workgroup per CU of a 256-CU device
+constexpr HlGeometry HLB_SELECT = {HLB_PM, HLB_TN, HLB_BLK_U4 * sizeof(uint4), true, HLB_KMAX, 1024};
 
 }  // namespace pm
 
 extern "C" size_t pm_hellinger_select_bf16_workspace(int nA, int nB, int n_frames, int k) {
-    if (nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 || k > pm::HLB_KMAX) return 0;
-    return pm::hlb_workspace(nA, nB, n_frames, k).bytes;
+    return pm::hl_layout(pm::HLB_SELECT, nA, nB, n_frames, k).bytes;
 }
 
 extern "C" int pm_hellinger_delta_bf16(double *delta1_host) {
@@ -437,19 +392,17 @@ extern "C" int pm_hellinger_select_bf16(const double *scA, int nA, const double 
                                         const double *v, int k, int split, int32_t *out_col, double *out_bound,
                                         int32_t *nonfinite1, void *ws, size_t ws_bytes, void *stream) {
     using namespace pm;
-    if (!scA || !scB || !out_col || !out_bound || !nonfinite1 || nA <= 0 || nB <= 0 || n_frames < 1 || n_frames > 4 || k < 1 ||
-        k > HLB_KMAX || split < 0 || (n_frames > 1 && frame_stride < (size_t)nB * PM_NBINS))
-        return PM_ERR_INVALID_ARG;
-    const HlbWorkspace L = hlb_workspace(nA, nB, n_frames, k);
-    if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < L.bytes) return PM_ERR_WORKSPACE;
+    const HlLayout L = hl_layout(HLB_SELECT, nA, nB, n_frames, k);
+    const bool args = scA && scB && out_col && out_bound && nonfinite1;
+    if (const int err = hl_check(args, L, nB, n_frames, split, frame_stride, ws, ws_bytes)) return err;
     hipStream_t s = (hipStream_t)stream;
     char *base = (char *)ws;
     uint4 *rA = (uint4 *)(base + L.rA), *rB = (uint4 *)(base + L.rB);
     double *hA = (double *)(base + L.hA), *hB = (double *)(base + L.hB);
     int32_t *pcol = (int32_t *)(base + L.pcol);
     double *pval = (double *)(base + L.pval);
-    const long PB = ((long)nA + HLB_PM - 1) / HLB_PM, CT = ((long)nB + HLB_TN - 1) / HLB_TN;
-    const int S = hlb_splits(split, PB, CT, n_frames), R = S * n_frames, RG = (R + HLB_XR - 1) / HLB_XR;
+    const long PB = L.PB, CT = L.CT;
+    const int S = hl_splits(HLB_SELECT, L, split, n_frames), R = S * n_frames, RG = (R + HLB_XR - 1) / HLB_XR;
     int32_t *oc = S == 1 ? out_col : pcol;
     double *ov = S == 1 ? out_bound : pval;
 

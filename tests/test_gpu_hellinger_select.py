@@ -144,3 +144,26 @@ def test_the_public_call(g):
     tc, tb = (x.cpu().numpy() for x in g.K.hellinger_topk(g.nat.to_dev(a), g.nat.to_dev(b), k=k))
     pc, lower = S.unary_distance_candidates(a, tuple(b), k=k)
     assert np.array_equal(pc, tc) and np.array_equal(lower, tb - delta)
+
+
+def test_a_tie_across_splits_is_broken_by_column(g):
+    """Fixed rows 20 and 100 are bit-identical copies of moving row 7: equal bounds, the smallest of the row.  With 130 fixed rows
+    the top-k kernel has three 64-row tiles and split 2 or 3 puts the two columns into different partial lists; the selection has
+    two 128-row tiles, so its splits run the merge as well.  One merge (hl_select_merge_kernel, with and without prices) serves
+    both: the lists are [20, 100, ...] with equal bounds, and the same bits for every split and from both calls."""
+    n, m, k = 70, 130, 4
+    a, b = synthetic_case(n, m, 1, 3)
+    b = b.copy()
+    b[0, 20] = b[0, 100] = a[7]
+    assert -(-m // 64) >= 3 and -(-m // 128) >= 2 and 20 // 64 != 100 // 64      # split 2 gives S = 2 in both, and cuts between them
+    ta, tb = g.nat.to_dev(a), g.nat.to_dev(b)
+    outs = []
+    for split in (1, 2, 3):
+        outs.append(tuple(x.cpu().numpy() for x in g.K.hellinger_topk(ta, tb, k=k, split=split)))
+        for v in (None, np.zeros((1, m))):
+            outs.append(select(g, ta, tb, v, k, split))
+    cols, bound = outs[0]
+    assert cols[0, 7, :2].tolist() == [20, 100] and bound[0, 7, 0].view(np.int64) == bound[0, 7, 1].view(np.int64)
+    assert bound[0, 7, 1] < bound[0, 7, 2]
+    for c2, b2 in outs[1:]:
+        assert np.array_equal(c2, cols) and np.array_equal(b2.view(np.int64), bound.view(np.int64))
