@@ -402,7 +402,9 @@ int pm_chi2_sym_table_info(const void *ws, int32_t *tabled30, int32_t *table_siz
 /* Report (benchmarks, tests): seeded30[g] = 1 if the last *_ws launch on this workspace could take shell g's reciprocals from the
  * count-sum table (seeded division): every value is count / total, BOTH clouds have the same total, and the shell's largest
  * count of the moving cloud plus that of the fixed cloud is below nseed = table_size^2.  Launch-wide; a tile seeds such a shell
- * only from its switch shell on (where it gives up its term table).  With unequal totals nothing is seeded.  Synchronises. */
+ * only from its switch shell on (where it gives up its term table).  With unequal totals nothing is seeded.  The seeding launches
+ * first certify on the device, for their own total and every count pair they can meet, that the seeded quotient has the bits of
+ * the computed one; where that certificate failed (or PM_CHI2_SEED_CERT=0 forced it to) no shell is reported.  Synchronises. */
 int pm_chi2_sym_seed_info(const void *ws, int32_t *seeded30, int32_t *nseed, void *stream);
 /* pm_chi2_cost8_sym_ws (pairing = -1: out = eight matrices) or pm_chi2_cost_pair_sym_ws (pairing = 0..3: out = two) with a
  * per-shell count of the tiles that served the shell from the table: tiles_tabled30 (device, 30 x uint32, may be NULL) is

@@ -202,34 +202,40 @@ struct SymMeta {
     unsigned long long minbits[2];     // smallest positive descriptor value of each cloud (bit pattern; +inf if none)
     double tot[2];                     // its reciprocal rounded to an integer: the candidate total
     int bad;                           // some value is not fl(count / total): no table
-    int pad;
+    int short_ok;                      // 1 until seed_cert_kernel finds a count pair whose short seeded division is not div_pos's: no seeds
     int maxc[2][CH_NSHELL];            // largest count per (r, theta) shell, saturated at 255
     unsigned short maxfull[2][CH_NSHELL];   // the same, saturated at 65 535 (seeded division: the sum of the two must stay below NSEED)
 };
 
 // SEEDED DIVISION (NSP > 0).  When both clouds have the same total T, a computed term's denominator fl(fl(ca/T) + fl(cb/T)) is
-// (s/T)(1 + 3 * 2^-53) with s = ca + cb, so a ONE-dimensional table R[s] = fl(T/s) seeds the reciprocal to 2^-51 and one Newton
-// step finishes it (pm_common.h: div_seeded, seed_offset): fma(index), ds_read_b64, fma, fma instead of v_rcp_f64, fma, fma, fma —
-// 11 VALU instructions at 4 issue cycles against 12 of which the reciprocal takes 16.  Same quotient bits: both reciprocals are
-// accurate enough for the residual correction to round correctly (seed_div_check.hip).  R overlays the term table: shell g may
-// be seeded iff meta->bad == 0, tot[0] == tot[1] and maxfull[0][g] + maxfull[1][g] < NSEED = TL * TL (launch-wide); a tile serves
+// (s/T)(1 + 3 * 2^-53) with s = ca + cb, so a ONE-dimensional table R[s] = fl(T/s) seeds the reciprocal to 2^-51 (pm_common.h:
+// seed_offset) and the quotient's residual correction runs on the seed itself (pm_seed_short.h: div_seeded_short): fma(index),
+// ds_read_b64 instead of v_rcp_f64, fma, fma, fma — 9 VALU instructions at 4 issue cycles against 12 of which the reciprocal
+// takes 16.  Same quotient bits, BY CERTIFICATE: no proof covers a 2^-51 reciprocal, so seed_cert_kernel below checks every count
+// pair the launch can meet against div_pos, for the launch's T, and clears meta->short_ok at the first difference; then nothing is
+// seeded.  R overlays the term table: shell g may be seeded iff meta->bad == 0, tot[0] == tot[1], meta->short_ok != 0 and
+// maxfull[0][g] + maxfull[1][g] < NSEED = TL * TL (launch-wide); a tile serves
 // shells below its switch shell g_sw as before (tabled where its mask says so, div_pos otherwise), refills `tab` with R at g_sw
 // between two barriers, and from there on serves eligible shells seeded and the others by div_pos; nothing is tabled from g_sw
 // on.  g_sw minimises the summed per-shell cost under the constants below (ties: the larger g_sw, i.e. the table is kept).
 // With unequal totals nothing is eligible, g_sw = CH_STAGES, and the kernel runs exactly as without NSP.  NSP = 4: every pairing
 // of a seeded shell goes through R; NSP = 2: pairings 0 and 1 do, 2 and 3 stay on div_pos (less LDS gather traffic, more VALU).
 // issue cycles per (pair, bin) of a shell: computed from the instruction model (12 VALU, the reciprocal at 16 cycles, four pairings);
-// tabled and seeded as measured against it (0.353 and 0.898 of a computed shell: tools/seeded_shell_cost.py,
-// profiles/seeded_shell_cost.txt; the seeded model said 176)
-constexpr int CH_COST_TABLED = 85, CH_COST_SEEDED = 216, CH_COST_COMPUTED = 240;
-// terms per software-pipelined part of a seeded (row, pairing) group: with 6 the 8-matrix kernel spills 42 registers, with 3 two,
-// with 2 none (254 of 256)
+// tabled and seeded as measured against it (0.353 and 0.770 of a computed shell: tools/seeded_shell_cost.py,
+// profiles/seed_short_bench.txt; 0.898 with the Newton step, profiles/seeded_shell_cost.txt)
+constexpr int CH_COST_TABLED = 85, CH_COST_SEEDED = 185, CH_COST_COMPUTED = 240;
+// terms per software-pipelined part of a seeded (row, pairing) group: with 6 the 8-matrix kernel spills 42 registers, with 4 nine,
+// with 3 two, with 2 none (254 of 256) — with and without the Newton step alike
 constexpr int CH_SEED_PART = 2;
 constexpr int CH_NSP_DEFAULT = 4;      // pairings per row the product's kernel seeds (PM_CHI2_SEED in the environment: 0, 2 or 4)
 inline int seed_pairings() {
     const char *e = getenv("PM_CHI2_SEED");                // (read per launch, as PM_CHI2_MAX_BLOCKS: a measurement and test knob)
     if (e && e[0] && !e[1] && (e[0] == '0' || e[0] == '2' || e[0] == '4')) return e[0] - '0';
     return CH_NSP_DEFAULT;
+}
+inline bool seed_cert_forced_off() {                       // PM_CHI2_SEED_CERT=0: the certificate reads 0 whatever the pairs say (test and timing knob)
+    const char *e = getenv("PM_CHI2_SEED_CERT");
+    return e && e[0] == '0' && !e[1];
 }
 
 // RELAX (round 4, opt-in, never the default): the same eight matrices WITHOUT the bit-identity contract — an experiment on what
@@ -357,7 +363,7 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
             // launch-wide eligibility, then the switch shell: cost(k) = shells below k as the mask says, shells from k on seeded
             // or computed; all of it wave-uniform (scalar loads of the header, scalar arithmetic)
             int smax = 0;
-            if (meta->bad == 0 && meta->tot[0] == meta->tot[1]) {
+            if (meta->bad == 0 && meta->tot[0] == meta->tot[1] && meta->short_ok != 0) {
                 for (int g = 0; g < CH_STAGES; ++g) {
                     const int s = (int)meta->maxfull[0][g] + (int)meta->maxfull[1][g];
                     if (s < TL * TL) {
@@ -591,7 +597,7 @@ __global__ __launch_bounds__(CH_THREADS, MINW) void chi2_sym_kernel(const double
                             const int p = (h % NP) * HK + k;
                             const int q = (t == 0) ? p : (t == 1) ? (p + 6) % 12 : (t == 2) ? 11 - p : (17 - p) % 12;
                             const double df = a[p] - b[q];
-                            T[p] = seeded ? div_seeded(df * df, a[p] + b[q], Rc[k]) : div_pos(df * df, a[p] + b[q]);
+                            T[p] = seeded ? div_seeded_short(df * df, a[p] + b[q], Rc[k]) : div_pos(df * df, a[p] + b[q]);
                         }
                         if (h % NP == NP - 1) {
                             const int hn = (TSEL < 0) ? t : 0, hr = (TSEL >= 0) ? 1 : (t == 0) ? 5 : (t == 1) ? 4 : (t == 2) ? 7 : 6;
@@ -874,7 +880,7 @@ __global__ void sym_meta_init_kernel(SymMeta *m) {
         m->minbits[t] = 0x7ff0000000000000ull;
         m->tot[t] = 0.0;
     }
-    if (t == 0) m->bad = 0, m->pad = 0;
+    if (t == 0) m->bad = 0, m->short_ok = 1;
     if (t < CH_NSHELL) {
         m->maxc[0][t] = m->maxc[1][t] = 0;
         m->maxfull[0][t] = m->maxfull[1][t] = 0;
@@ -961,6 +967,35 @@ __global__ __launch_bounds__(256) void counts_extract_kernel(const double *__res
 }
 static_assert(offsetof(SymMeta, maxfull) % 4 == 0 && (CH_NSHELL * sizeof(unsigned short)) % 4 == 0, "maxfull[which] starts on a dword");
 
+// The certificate of the short seeded division (div_seeded_short), for THIS launch: one workgroup per moving count ca, its threads
+// stride over the fixed count cb, and every pair a seeded term of this launch can have — ca <= CA, cb <= CB, ca + cb < NSEED, CA and
+// CB the largest per-shell maxima of the two clouds over the shells chi2_sym_kernel may seed — goes through seed_short_pair_ok
+// with the launch's total and the seed chi2_sym_kernel puts into R[s].  At most NSEED (NSEED + 1) / 2 = 39 M pairs.  meta->short_ok
+// is 1 from sym_meta_init_kernel; it is cleared by a failing pair, by unusable counts or unequal totals (nothing is seeded then
+// anyway) and by the knob.  Runs after counts_extract_kernel and before chi2_sym_kernel, on their stream.
+__global__ __launch_bounds__(256) void seed_cert_kernel(SymMeta *m, int forced_off) {
+    constexpr int NSEED = CH_TL * CH_TL;
+    const int ca = blockIdx.x;
+    if (forced_off || m->bad != 0 || m->tot[0] != m->tot[1]) {
+        if (ca == 0 && threadIdx.x == 0) m->short_ok = 0;
+        return;
+    }
+    int CA = -1, CB = -1;
+    for (int g = 0; g < CH_NSHELL; ++g) {
+        const int ma = m->maxfull[0][g], mb = m->maxfull[1][g];
+        if (ma + mb < NSEED) CA = max(CA, ma), CB = max(CB, mb);
+    }
+    if (ca > CA) return;
+    const double T = m->tot[0];
+    bool ok = true;
+    for (int cb = threadIdx.x; cb <= CB && ca + cb < NSEED; cb += 256) {
+        const int s = ca + cb;
+        const double r0 = s ? div_pos(T, (double)s) : 1.0;       // R[s], as chi2_sym_kernel fills it
+        ok = seed_short_pair_ok(ca, cb, T, &r0, s, [](double n, double d) { return div_pos(n, d); }) && ok;
+    }
+    if (!ok) m->short_ok = 0;
+}
+
 constexpr size_t SYM_META_BYTES = 512;
 static_assert(sizeof(SymMeta) <= SYM_META_BYTES, "workspace header");
 
@@ -994,6 +1029,7 @@ int sym_product_launch(int nsp, const double *sc_m1, int nM, const double *sc_f1
     constexpr int OFF = (TSEL < 0) ? -3 : TSEL + 4, OTHER = (TSEL < 0) ? -2 : TSEL;
     if (nsp == 0)
         return chi2_sym_launch<4, 2, OFF, CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, mstride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, report);
+    seed_cert_kernel<<<CH_TL * CH_TL, 256, 0, s>>>(w.meta, seed_cert_forced_off() ? 1 : 0);      // every seeding kernel is launched below: none without its certificate
     if (TSEL < 0 && nsp != CH_NSP_DEFAULT)
         return chi2_sym_launch<4, 2, OTHER, CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, mstride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, report);
     return chi2_sym_launch<4, 2, TSEL, CH_TL>(sc_m1, nM, sc_f1, nF, out, ld, mstride, s, w.cntA, w.cntB, w.meta, nullptr, nullptr, report);
@@ -1056,7 +1092,7 @@ extern "C" int pm_chi2_sym_seed_info(const void *ws, int32_t *seeded30, int32_t 
     }
     constexpr int NSEED = pm::CH_TL * pm::CH_TL;
     for (int g = 0; g < pm::CH_NSHELL; ++g)
-        seeded30[g] = (m.bad == 0 && m.tot[0] == m.tot[1] && (int)m.maxfull[0][g] + (int)m.maxfull[1][g] < NSEED) ? 1 : 0;
+        seeded30[g] = (m.bad == 0 && m.tot[0] == m.tot[1] && m.short_ok != 0 && (int)m.maxfull[0][g] + (int)m.maxfull[1][g] < NSEED) ? 1 : 0;
     *nseed = NSEED;
     return PM_OK;
 }

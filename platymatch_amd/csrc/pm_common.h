@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/platymatch_hip.h"
+#include "pm_seed_short.h"
 
 #define PM_WAVE 64
 
@@ -72,6 +73,11 @@ __device__ __forceinline__ double div_pos(double n, double d) {
 // d = 1e-300, n = 1e-600 = 0): R[0] = 1 gives r = 2, q = 0, res = 0, result +0 = 0 / 1e-300.  Checked bit for bit against IEEE
 // division over every (ca, cb) with ca + cb < 8 836 for several totals, on the device and on the host
 // (tools/microbench/seed_div_check.hip, run by the test-suite both ways).
+// The chi-square kernels no longer call it: they divide by div_seeded_short (pm_seed_short.h: the same tail on r0 itself, no
+// Newton step), which has no such argument behind it and is therefore CERTIFIED per launch — seed_cert_kernel (pm_chi2.hip)
+// evaluates seed_short_pair_ok on the device for every count pair the launch can meet, with the launch's own T, before the cost
+// kernel starts; one failing pair and the launch seeds nothing (every term by div_pos, as under PM_CHI2_SEED=0).  div_seeded
+// stays as the proven sequence the microbenchmark and its test hold against IEEE division.
 __device__ __forceinline__ double div_seeded(double n, double d, double r0) {
     const double e = __builtin_fma(-d, r0, 1.0);
     const double r = __builtin_fma(r0, e, r0);
